@@ -1,7 +1,13 @@
 """Benchmark: two-tower DSSM training samples/sec on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2] [--batch 4096]
+    python bench.py ... --dump-outputs DIR     (the last timed step's outputs as DIR/<name>.npy)
+    python bench.py ... --full                 (+ measured peaks, per-kernel times and rooflines,
+                                                the other workloads, the CPU baselines)
     torchrun --nproc-per-node N bench.py --gpus N ...       (one process per GPU, RCCL)
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else the
+benchmark measures runs only with --full.
 
 `python bench.py --gpus N` (N > 1, no torchrun) launches the N rank processes itself
 (launch_ranks) and forwards rank 0's line.
@@ -88,7 +94,7 @@ def parse():
     ap.add_argument('--batches', type=int, default=8,
                     help='distinct resident batches cycled through by the timed steps')
     ap.add_argument('--extra', default=None,
-                    help='comma-separated further workloads reported in the same JSON line under '
+                    help='with --full: comma-separated further workloads reported in the same JSON line under '
                          '"extra", each NAME or NAME:DTYPE (default when --config is c2: c3 at fp32, the '
                          "reference's precision and the credited C3 number, and c3:bf16 beside it)")
     ap.add_argument('--prof-markers', action='store_true',
@@ -104,8 +110,23 @@ def parse():
     ap.add_argument('--traffic', default='auto',
                     help='PMC traffic summary (tools/pmc_traffic.py output) for roofline.traffic; '
                          'auto: profiles/traffic_<config>_<dtype>.json when it matches this run')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline figure: the on-device peak measurements, the '
+                         'instrumented passes (per-kernel times and rooflines), the --extra workloads and '
+                         'the CPU baselines, with the whole record on stderr ({"bench_detail": ...}). '
+                         'Without it the run sets up, warms up, times --steps steps and prints the line')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write what the last timed step of the --config workload '
+                         'computed as DIR/<name>.npy (float32; see dump_outputs). Such a run steps in the '
+                         'deterministic mode (RSYS_DETERMINISTIC=1: fixed-order table gradients, 3.5 %% '
+                         'slower at C2) so that its outputs are the same every run; RSYS_DETERMINISTIC=0 in '
+                         'the environment dumps from the default kernels instead (run-to-run noise ~2e-3)')
     ap.add_argument('--cpu-worker', nargs=2, default=None, metavar=('SPEC', 'OUT'), help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if not a.full:
+        if a.extra:
+            ap.error('--extra workloads run only with --full')
+        a.extra = ''
     if a.extra is None:
         if a.config == 'c2' and a.batch is None and not a.zipf:
             # N = 1 (the driver's BENCH line): every BASELINE workload that fits one GPU -- C3 at fp32
@@ -463,9 +484,47 @@ def optimizer_roofline(summ, rows, flat_numel, dense_numel, ms_step, args, B, na
                      'towers serial (instrumented pass)'}
 
 
-def run_workload(args, name, dtype, zipf, hard_negatives, rank, world, dev, cpu_seconds, peaks=None):
+DUMP_MAX_BYTES = 64 << 20  # of all the --dump-outputs files together
+
+
+def dump_outputs(out_dir, loss, emb, model):
+    """--dump-outputs: what the last timed step computed, as float32 .npy files in `out_dir`, so two
+    builds run with the same arguments (hence the same seeded model and batches, and, in the
+    deterministic mode main() sets for such a run, the same bits every run) can be compared array
+    for array:
+      loss.npy      [1]     the step's loss
+      user_emb.npy  [B, D]  the user tower's output of the step's batch
+      item_emb.npy  [B, D]  the item tower's
+      params.npy    [n]     the model after the step: every floating-point state_dict() tensor,
+                            flattened and concatenated in state_dict order; a tensor above the cap
+                            (2^20 elements, halved until all files fit DUMP_MAX_BYTES) contributes
+                            that many elements at fixed positions (torch.Generator seed 0) instead."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    U, I = emb
+    arrays = {'loss': loss.detach().reshape(1), 'user_emb': U.detach(), 'item_emb': I.detach()}
+    sd = [v.detach().reshape(-1) for v in model.state_dict().values() if v.is_floating_point()]
+    budget = DUMP_MAX_BYTES // 4 - sum(int(a.numel()) for a in arrays.values()) - 1024  # .npy headers
+    cap = 1 << 20
+    while sum(min(int(v.numel()), cap) for v in sd) > budget:
+        cap //= 2
+    g = torch.Generator().manual_seed(0)
+    parts = []
+    for v in sd:
+        if v.numel() > cap:
+            v = v[torch.randint(int(v.numel()), (cap,), generator=g).to(v.device)]
+        parts.append(v.float().cpu())
+    arrays['params'] = torch.cat(parts)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + '.npy'), a.float().cpu().numpy())
+    print(f'[bench] outputs of the last timed step written to {out_dir}: ' +
+          ', '.join(f'{k}{list(a.shape)}' for k, a in arrays.items()), file=sys.stderr, flush=True)
+
+
+def run_workload(args, name, dtype, zipf, hard_negatives, rank, world, dev, cpu_seconds, peaks=None, dump_dir=None):
     """Build the model of workload `name`, time args.steps steps (after args.warmup) cycling through
-    args.batches distinct resident batches, profile one instrumented pass. Returns the result dict
+    args.batches distinct resident batches; with `dump_dir`, write the last timed step's outputs
+    there (dump_outputs); with args.full, profile one instrumented pass. Returns the result dict
     on rank 0 (None elsewhere); with args.pmc_bracket, prints the bracket line and returns None."""
     cfg = load_cfg(name, args)
     if rank == 0:
@@ -520,11 +579,15 @@ def run_workload(args, name, dtype, zipf, hard_negatives, rank, world, dev, cpu_
         neg_sets = [torch.randint(1, V, (B, hard_negatives), device=dev, generator=g) for _ in range(K)]
         neg_ids = neg_sets[0].clone()
 
+    last_emb = []
+
     def fwd_bwd():
         opt.zero_grad()
         if catalog is not None:
             batch['hard_negatives'] = catalog.materialize(neg_ids)
         U, I, H = model(batch)
+        if dump_dir:  # the step's tower outputs (under a captured graph: its static output tensors)
+            last_emb[:] = [U, I]
         loss = model.compute_loss(U, I, item_ids=ids, hard_neg_emb=H, temperature=T)
         with rdist.overlap(model):  # N > 1: each tower's all-reduce starts inside the backward
             loss.backward(backward_seed(loss))
@@ -668,10 +731,33 @@ def run_workload(args, name, dtype, zipf, hard_negatives, rank, world, dev, cpu_
     el = float(el_t.item())
     final_loss = float(loss.item())
     if rank == 0:
-        print(f'[bench] {name} {dtype}: {1e3 * el / args.steps:.3f} ms/step; instrumented passes next',
-              file=sys.stderr, flush=True)
+        print(f'[bench] {name} {dtype}: {1e3 * el / args.steps:.3f} ms/step' +
+              ('; instrumented passes next' if args.full else ''), file=sys.stderr, flush=True)
     model.check_errors()  # device error flags (bad ids, NaN embeddings) of the timed steps
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, loss, last_emb, model)
+    prof = instrumented_pass(args, name, dtype, zipf, hard_negatives, B, peaks, model, el, next_batch, fwd_bwd,
+                             allreduce, opt_step) if args.full else None
+    used_graph = graphs is not None
+    _COPY_PLANS.clear()  # the plans hold this workload's batch tensors (and key on their ids)
+    if graphs is not None:  # the graphs (and the RCCL kernels they hold at N > 1) go first
+        torch.cuda.synchronize()
+        for g in graphs[:2]:
+            if g is not None:
+                g.reset()
+    del model, opt, batches, batch, graphs, catalog, last_emb
+    torch.cuda.empty_cache()
+    if rank != 0:
+        return None
+    return result_record(args, cfg, name, dtype, zipf, hard_negatives, world, B, K, el, t_issue, final_loss,
+                         used_graph, n_sharded, prof)
 
+
+def instrumented_pass(args, name, dtype, zipf, hard_negatives, B, peaks, model, el, next_batch, fwd_bwd, allreduce,
+                      opt_step):
+    """--full only, after the timed steps: three eager steps of the workload under a KernelTimer
+    (`next_batch`, `fwd_bwd`, `allreduce`, `opt_step`: run_workload's step pieces), and from them
+    the per-kernel times and every roofline object of the record (`el`: the timed steps' seconds)."""
     # roofline of the dominant kernel: HIP events on the launch stream, eager instrumented steps.
     # A spin kernel first gives the host a head start: the launches (Python + ctypes, slower than
     # the small tower kernels themselves) then queue up behind it and the GPU runs them back to
@@ -814,19 +900,23 @@ def run_workload(args, name, dtype, zipf, hard_negatives, rank, world, dev, cpu_
 
     opt_roof = optimizer_roofline(summ, lazy_rows, flat_numel, dense_numel, ms_step=el / args.steps * 1e3,
                                   args=args, B=B, name=name, dtype=dtype, zipf=zipf, hard_negatives=hard_negatives)
-    used_graph = graphs is not None
-    _COPY_PLANS.clear()  # the plans hold this workload's batch tensors (and key on their ids)
-    if graphs is not None:  # the graphs (and the RCCL kernels they hold at N > 1) go first
-        torch.cuda.synchronize()
-        for g in graphs[:2]:
-            if g is not None:
-                g.reset()
-    del model, opt, batches, batch, graphs, catalog
-    torch.cuda.empty_cache()
-    cpu = None
+    return {
+        'roofline': roof,
+        'gather_roofline': gather_roof,
+        'batch_dot_roofline': batch_dot or None,
+        'softmax_roofline': softmax or None,
+        'step_roofline': step_roof,
+        'optimizer_roofline': opt_roof,
+        'cpu_baseline': None,
+        'kernel_ms_per_step': {k: round(v['ms'] / 3, 4) for k, v in sorted(summ.items(), key=lambda kv: -kv[1]['ms'])},
+        '_gemm_shapes': kt.gemm_shapes() if os.environ.get('RSYS_BENCH_DETAIL') else None,
+    }
 
-    if rank != 0:
-        return None
+
+def result_record(args, cfg, name, dtype, zipf, hard_negatives, world, B, K, el, t_issue, final_loss, used_graph,
+                  n_sharded, prof):
+    """One workload's record: the headline fields, and with --full the instrumented pass's objects
+    (`prof`) after them."""
     samples = world * B * args.steps
     tp = cfg['two_tower']['user_tower'].get('transformer_parameters', {})
     has_seq = bool(cfg['two_tower']['user_tower'].get('sequence_features'))
@@ -847,16 +937,9 @@ def run_workload(args, name, dtype, zipf, hard_negatives, rank, world, dev, cpu_
                    'ids': f'zipf({zipf})' if zipf else 'uniform',
                    'hard_negatives': hard_negatives, 'resident_batches': K,
                    'gpu_max_hw_queues': os.environ.get('GPU_MAX_HW_QUEUES', 'unset (HIP default 4)'),
-                   'row_sharded_tables': n_sharded},
-        'roofline': roof,
-        'gather_roofline': gather_roof,
-        'batch_dot_roofline': batch_dot or None,
-        'softmax_roofline': softmax or None,
-        'step_roofline': step_roof,
-        'optimizer_roofline': opt_roof,
-        'cpu_baseline': cpu,
-        'kernel_ms_per_step': {k: round(v['ms'] / 3, 4) for k, v in sorted(summ.items(), key=lambda kv: -kv[1]['ms'])},
-        '_gemm_shapes': kt.gemm_shapes() if os.environ.get('RSYS_BENCH_DETAIL') else None,
+                   'row_sharded_tables': n_sharded,
+                   'deterministic': os.environ.get('RSYS_DETERMINISTIC', '0') == '1'},
+        **(prof or {}),
     }
 
 
@@ -917,17 +1000,21 @@ def _extra_short(r):
             'cpu_baseline_of': r.get('cpu_baseline_of', r['config']['workload'].split(':')[0])}
 
 
-def compact_line(out):
-    """The stdout line: the contract's fields, the dominant kernel's roofline without its PMC
-    detail, the CPU baseline's numbers, and per extra workload its headline numbers only (the
-    whole record is the stderr 'bench_detail' object). Kept well under 8 KB."""
+def compact_line(out, full=True):
+    """The stdout line: the contract's fields and the run's configuration; with --full also the
+    dominant kernel's roofline without its PMC detail, the CPU baseline's numbers, and per extra
+    workload its headline numbers only (the whole record is the stderr 'bench_detail' object).
+    Kept well under 8 KB."""
     keys = ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling',
             'vs_baseline', 'dtype', 'data')
     line = {k: out[k] for k in keys}
     cfg = out['config']
     line['config'] = {k: cfg.get(k) for k in ('workload', 'global_batch', 'per_gpu_batch', 'seq_len', 'dropout',
                                              'parallelism', 'hip_graph', 'ids', 'hard_negatives',
-                                             'resident_batches', 'row_sharded_tables')}
+                                             'resident_batches', 'row_sharded_tables', 'deterministic')}
+    if not full:
+        line['wall_s'] = out.get('wall_s')
+        return line
     line['roofline'] = {k: v for k, v in out['roofline'].items() if k not in ('traffic_detail', 'valu_exp')}
     g = out.get('gather_roofline') or {}
     line['gather_roofline'] = {k: {'frac': v.get('frac'), 'achieved': v.get('achieved'), 'ms_per_step': v.get('ms_per_step'),
@@ -1017,7 +1104,18 @@ def main():
     env_world = int(os.environ.get('WORLD_SIZE', '1'))
     if args.gpus is not None and args.gpus != env_world:  # before the CPU worker or any HIP call
         raise SystemExit(f'bench.py: --gpus {args.gpus} but the process group has {env_world} ranks')
-    cpu_s = 0.0 if args.no_cpu_baseline else args.cpu_baseline_seconds
+    if args.dump_outputs and env_world > 1:
+        raise SystemExit('bench.py: --dump-outputs writes one process\'s outputs; run it with --gpus 1')
+    if args.dump_outputs:
+        # Outputs that are the same every run: the ordinary tables' gradients go through the
+        # fixed-order kernels instead of the float-atomic scatter ("Table gradients"),
+        # whose last-bit differences bf16 rounding and Adam otherwise grow to 2e-3 within 25 steps;
+        # the step is then 3.5 % slower than a plain run's (both measured: profiles/
+        # dump_outputs_determinism.txt), and the line says so (config.deterministic). Set before the
+        # library's first call. RSYS_DETERMINISTIC=0 in the environment keeps the default kernels:
+        # the dump then comes from the very path a plain run times, with that run-to-run noise.
+        os.environ.setdefault('RSYS_DETERMINISTIC', '1')
+    cpu_s = args.cpu_baseline_seconds if args.full and not args.no_cpu_baseline else 0.0
     worker = None
     if int(os.environ.get('WORLD_SIZE', '1')) == 1 and cpu_s > 0 and not args.pmc_bracket:
         # before any HIP call of this process: the CPU baselines run beside the GPU timing
@@ -1033,9 +1131,9 @@ def main():
     torch.cuda.set_device(dev)
     if args.dtype == 'config':
         args.dtype = 'bf16' if args.config in ('c2', 'c3', 'c5') else 'fp32'
-    peaks = None if args.pmc_bracket else measure_peaks(dev)
+    peaks = measure_peaks(dev) if args.full and not args.pmc_bracket else None
     out = run_workload(args, args.config, args.dtype, args.zipf, args.hard_negatives, rank, world, dev,
-                       cpu_s, peaks)
+                       cpu_s, peaks, dump_dir=args.dump_outputs)
     if args.pmc_bracket:
         _teardown()
         return
@@ -1100,7 +1198,10 @@ def main():
                     if nm != key:
                         extras[key]['cpu_baseline_of'] = nm
             out['c1_cpu_baseline'] = cpu.get('c1')
-    if rank == 0:
+    if rank == 0 and not args.full:
+        out['wall_s'] = round(time.time() - T_START, 1)
+        print(json.dumps(compact_line(out, full=False)), flush=True)
+    elif rank == 0:
         out['peaks_measured'] = peaks
         if args.prof_markers:
             out['prof_marker_order'] = order

@@ -68,19 +68,19 @@ def test_param_count_demo_schema():
     assert sum(p.numel() for p in m.parameters()) == 886540  # SURVEY §8b (measured on the reference)
 
 
-@pytest.mark.skipif(not os.path.isdir('/root/reference'), reason='reference only in the build container')
 def test_initial_weights_identical_to_reference_under_same_seed():
-    import sys
-    sys.path.insert(0, '/root/reference')
-    from project.models.TwoTower.GenericTower import GenericTower as RG
-    from project.models.TwoTower.TwoTowerModel import TwoTowerModel as RM
-    cfg = yaml.safe_load(open(os.path.join(ROOT, 'configs', 'demo.yaml')))
-    torch.manual_seed(11)
-    ref = RM(RG(cfg, 'user_tower'), RG(cfg, 'item_tower')).state_dict()
-    torch.manual_seed(11)
+    """Bit for bit: the reference's own initial state_dict under the same seed is recorded as one
+    SHA-256 per tensor in tests/golden/init_demo_seed11.json (tests/golden/make_init_golden.py)."""
+    import json
+    from make_init_golden import tensor_digests
+    gold = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'init_demo_seed11.json')))
+    cfg = yaml.safe_load(open(os.path.join(ROOT, 'configs', gold['config'] + '.yaml')))
+    torch.manual_seed(gold['seed'])
     ours = TwoTowerModel(GenericTower(cfg, 'user_tower'), GenericTower(cfg, 'item_tower')).state_dict()
+    got, ref = tensor_digests(ours), gold['tensors']
+    assert list(got) == list(ref)
     for k in ref:
-        assert torch.equal(ref[k], ours[k]), k
+        assert got[k] == ref[k], k
 
 
 def test_cpu_tensors_fail_loudly():

@@ -757,7 +757,7 @@ def test_bench_two_ranks_gloo_one_gpu(tmp_path, launcher):
     for k in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_PORT'):
         env.pop(k, None)
     args = [os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '2', '--config', 'c2',
-            '--no-cpu-baseline', '--extra=']
+            '--full', '--no-cpu-baseline', '--extra=']  # --full: the instrumented eager steps at N > 1 too
     if launcher == 'torchrun':
         cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2',
                '--master-addr', '127.0.0.1', '--master-port', str(port)] + args
@@ -1022,7 +1022,7 @@ def test_bench_four_ranks_c3_row_sharded_gloo_one_gpu():
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '4',
            '--master-addr', '127.0.0.1', '--master-port', str(port), os.path.join(ROOT, 'bench.py'),
            '--gpus', '4', '--steps', '2', '--warmup', '1', '--config', 'c3', '--dtype', 'fp32',
-           '--no-cpu-baseline', '--extra=']
+           '--full', '--no-cpu-baseline', '--extra=']  # --full: the instrumented pass over the sharded tables
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=560)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]

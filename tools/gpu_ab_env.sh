@@ -1,7 +1,8 @@
 #!/bin/bash
 # env A/B of the bench line: bash tools/gpu_ab_env.sh "label=ENV1=v,ENV2=v label2=..." "config:dtype ..."
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
-mkdir -p gpurun_out
+OUT=${OUT:-prof_out}  # logs and the result table go here (git-ignored)
+mkdir -p $OUT
 VARS=$1; CFGS=${2:-c3:fp32}
 for rep in $(seq 1 ${REPS:-2}); do
 for cd in $CFGS; do
@@ -9,8 +10,8 @@ for cd in $CFGS; do
   for v in $VARS; do
     lab=${v%%=*}; envs=${v#*=}; [ "$envs" = "$v" ] && envs=""
     ( for kv in ${envs//,/ }; do export "$kv"; done
-      timeout -k 10 240 python bench.py --config $cfg --dtype $dt --no-cpu-baseline --extra= > gpurun_out/ab_${lab}_${cfg}_${dt}.log 2>&1 ) || { tail -5 gpurun_out/ab_${lab}_${cfg}_${dt}.log; exit 1; }
-    python3 - "$rep" "$cfg" "$dt" "$lab" gpurun_out/ab_${lab}_${cfg}_${dt}.log <<'PY' | tee -a gpurun_out/ab_env.txt
+      timeout -k 10 240 python bench.py --config $cfg --dtype $dt --full --no-cpu-baseline --extra= > $OUT/ab_${lab}_${cfg}_${dt}.log 2>&1 ) || { tail -5 $OUT/ab_${lab}_${cfg}_${dt}.log; exit 1; }
+    python3 - "$rep" "$cfg" "$dt" "$lab" $OUT/ab_${lab}_${cfg}_${dt}.log <<'PY' | tee -a $OUT/ab_env.txt
 import json, sys
 rep, cfg, dt, lab, path = sys.argv[1:]
 d = [json.loads(l)['bench_detail'] for l in open(path) if l.startswith('{"bench_detail"')][-1]

@@ -7,13 +7,16 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd)
 mkdir -p gpurun_out
 TREES=$1; CFGS=${2:-c3:fp32}
+# the per-kernel times read below need --full; a tree from before that option always ran them and
+# does not know it: FULL= (all trees) or FULL_<label>= (that tree, e.g. FULL_old=) leaves it out
+FULL=${FULL---full}
 for rep in $(seq 1 ${REPS:-3}); do
 for cd in $CFGS; do
   cfg=${cd%%:*}; dt=${cd#*:}
   for tv in $TREES; do
-    lab=${tv%%=*}; dir=${tv#*=}
+    lab=${tv%%=*}; dir=${tv#*=}; fv=FULL_$lab
     log=$ROOT/gpurun_out/abt_${lab}_${cfg}_${dt}_${rep}.log
-    ( cd $ROOT/$dir && timeout -k 10 240 python bench.py --config $cfg --dtype $dt --no-cpu-baseline --extra= ) > $log 2>&1 \
+    ( cd $ROOT/$dir && timeout -k 10 240 python bench.py --config $cfg --dtype $dt ${!fv-$FULL} --no-cpu-baseline --extra= ) > $log 2>&1 \
       || { tail -5 $log; exit 1; }
     python3 - "$rep" "$cfg" "$dt" "$lab" $log <<'PY' | tee -a $ROOT/gpurun_out/abt.txt
 import json, sys

@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd)
 mkdir -p gpurun_out/prof
 export TMPDIR=/tmp
-B="bench.py --steps ${STEPS:-10} --warmup 3 --no-cpu-baseline --prof-markers ${BENCH_ARGS}"
+B="bench.py --steps ${STEPS:-10} --warmup 3 --full --no-cpu-baseline --prof-markers ${BENCH_ARGS}"
 if [ -z "$NOTRACE" ]; then
 ( cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -d $ROOT/gpurun_out/prof/trace -o run --output-format csv -- python3 $ROOT/$B ) > gpurun_out/prof/trace.log 2>&1
 rc=$?; echo "trace rc=$rc"; tail -3 gpurun_out/prof/trace.log; [ $rc -eq 0 ] || exit $rc

@@ -1,6 +1,9 @@
 #!/bin/bash
 # Kernel-trace profile (rocprofv3 --kernel-trace --stats) of a short bench run, for
 # tools/step_timeline.py. Usage: tools/gpu_trace.sh <config> [extra bench args]
+# The trace holds the one config's plain run (set-up, warm-up, timed steps), which is what the
+# timeline reads; give `--full` (and `--extra ...`) among the bench args to trace the instrumented
+# passes and the other workloads as well.
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 ROOT=$(pwd)
 CFG=${1:-c2}; shift
