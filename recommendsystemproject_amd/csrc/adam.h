@@ -19,6 +19,13 @@ struct AdamConst {
   float one_m_b1, b2, one_m_b2, eps, wd;
 };
 
+// the step index clamped into the constants table (sparse.hip adam_prepare_kernel: consts[0].x
+// holds the table's length)
+__device__ __forceinline__ int clamp_step(const float2* consts, int64_t t) {
+  const int cap = __float_as_int(consts[0].x);
+  return t < cap ? (int)t : cap - 1;
+}
+
 __device__ __forceinline__ void adam_update(const AdamConst& h, float step_size, float inv_bc2_sqrt,
                                             float gs, float& p, float& m, float& v) {
 #pragma clang fp contract(off)  // no fma contraction whatever the including file says

@@ -12,6 +12,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma.h"
 #include "rng.h"
 
 namespace rs {
@@ -201,7 +202,7 @@ __global__ __launch_bounds__(256) void attn_bwd_kernel(const float* __restrict__
 // fragment of P V (k = key index), no data movement. Fragment loads are float4 rows of qkv:
 // lane (r = lane & 15, q = lane >> 4) holds X[row 16 t + r][4q .. 4q + 3], and MFMA s of a
 // 4-step k chain consumes component s (k = 4q + s), the permuted-k order used by rowgemm.
-typedef float f4 __attribute__((ext_vector_type(4)));
+typedef floatx4 f4;
 constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
 // LDS row pitch of the per-wave [L][16] tiles: lanes (c, q) read rows 4q + s, so a pitch of 20
 // words puts the four q groups on disjoint bank quarters (16 words would be a 4-way conflict)
@@ -210,17 +211,8 @@ constexpr int kRowP = 20;
 // dropout index ((b*H + h)*L + i)*L + j in 32 bits (the host checks B*H*L*L < 2^32):
 // keep_mult32 (rng.h)
 
-__device__ __forceinline__ f4 ld4(const float* p) { return *reinterpret_cast<const f4*>(p); }
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
-}
-__device__ __forceinline__ float xsum(float v) {
-  v += __shfl_xor(v, 16, 64);
-  return v + __shfl_xor(v, 32, 64);
-}
-__device__ __forceinline__ float xmax(float v) {
-  v = fmaxf(v, __shfl_xor(v, 16, 64));
-  return fmaxf(v, __shfl_xor(v, 32, 64));
 }
 
 // one wave per (b, h); 4 waves per workgroup = 4 consecutive (b, h) (the heads of one sample)
@@ -280,7 +272,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(
 #pragma unroll
       for (int e = 0; e < 4; ++e)
         if (kok[tk][e]) m = fmaxf(m, sv[tk][e] * scale2);
-    m = xmax(m);
+    m = quad_max(m);
     float l = 0.f;
     const int i = tq * 16 + r;
     const uint32_t rowbase = ((uint32_t)bh * (uint32_t)L + (uint32_t)i) * (uint32_t)L;
@@ -295,7 +287,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(
         sv[tk][e] = DROP ? pv * mk[e] : pv;
       }
     }
-    l = xsum(l);
+    l = quad_sum(l);
     // O[i][c] = sum_j pz[i][j] V[j][c]: A = this lane's probabilities (row i = lane & 15,
     // k = key), B = V[key][c = lane & 15]
     f4 o = {0.f, 0.f, 0.f, 0.f};
@@ -355,7 +347,7 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(
     *reinterpret_cast<f4*>(&Ks[row][4 * q]) = kf[t];
     *reinterpret_cast<f4*>(&Gs[row][4 * q]) = gf[t];
     // D_i = sum_c dO[i][c] O[i][c] (query i = row, this lane's 4 columns, then across q)
-    Di[t] = xsum(gf[t][0] * of[0] + gf[t][1] * of[1] + gf[t][2] * of[2] + gf[t][3] * of[3]);
+    Di[t] = quad_sum(gf[t][0] * of[0] + gf[t][1] * of[1] + gf[t][2] * of[2] + gf[t][3] * of[3]);
     lsei[t] = ok ? lse[(int64_t)bh * L + row] * kLog2e : 0.f;  // base-2 log-sum-exp
   }
   bool kok[NT][4];
@@ -457,24 +449,22 @@ __global__ __launch_bounds__(256) void attn_bwd_mfma_kernel(
 // f32 kernels feed one k-slice at a time, so Q/K/V/dO rows load as before and the softmax /
 // dropout / dS arithmetic (fp32) is unchanged. The B operands that need a column per lane
 // (V for P V; K, Q, dO for dQ, dK, dV) are read once per wave through LDS before the loops.
-typedef short s4v __attribute__((ext_vector_type(4)));
-typedef __bf16 bf4v __attribute__((ext_vector_type(4)));
 
 // two v_cvt_pk_bf16_f32 (round to nearest even, as the element-wise casts; those compiled to four
 // single-element converts and two v_perm_b32)
-__device__ __forceinline__ s4v bf4(const f4& v) {
+__device__ __forceinline__ shortx4 bf4(const f4& v) {
   typedef __bf16 bf2v __attribute__((ext_vector_type(2)));
   typedef float f2v __attribute__((ext_vector_type(2)));
   const bf2v lo = __builtin_convertvector(f2v{v[0], v[1]}, bf2v);
   const bf2v hi = __builtin_convertvector(f2v{v[2], v[3]}, bf2v);
-  return __builtin_bit_cast(s4v, __builtin_shufflevector(lo, hi, 0, 1, 2, 3));
+  return __builtin_bit_cast(shortx4, __builtin_shufflevector(lo, hi, 0, 1, 2, 3));
 }
-__device__ __forceinline__ f4 mfma16(const s4v& a, const s4v& b, const f4& c) {
+__device__ __forceinline__ f4 mfma16(const shortx4& a, const shortx4& b, const f4& c) {
   return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
 }
 // column r, rows 16t + 4q + j of a per-wave [LP][P] fp32 image
 template <int NT, int P>
-__device__ __forceinline__ void col_frags(const float* X, int r, int q, s4v (&out)[NT]) {
+__device__ __forceinline__ void col_frags(const float* X, int r, int q, shortx4 (&out)[NT]) {
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     f4 v;
@@ -486,11 +476,6 @@ __device__ __forceinline__ void col_frags(const float* X, int r, int q, s4v (&ou
 
 // qkv / dqkv storage: fp32, or bf16 (RS_ATTN_QKV_BF16). Q, K and V are only ever MFMA operands
 // here (rounded to bf16 by bf4), so bf16 storage gives the same products with half the bytes.
-__device__ __forceinline__ f4 ldq(const float* p) { return ld4(p); }
-__device__ __forceinline__ f4 ldq(const __bf16* p) {
-  const bf4v h = *reinterpret_cast<const bf4v*>(p);  // 8-byte load; bf16 -> fp32 is exact
-  return f4{(float)h[0], (float)h[1], (float)h[2], (float)h[3]};
-}
 __device__ __forceinline__ void stq(float* p, float v) { *p = v; }
 __device__ __forceinline__ void stq(__bf16* p, float v) { *p = (__bf16)v; }
 
@@ -554,10 +539,9 @@ __device__ __forceinline__ float vmax(float a, float b) { return __builtin_eleme
 // (r, q) receives W[4q + j][16 tk + r], j < 4 -- the A operand [key r][query 4q + j] of a product
 // that sums over the tile's queries (ds_read_b64_tr_b16; EXEC must be full: the callers' waves
 // exit whole or not at all)
-__device__ __forceinline__ s4v tr_col(const __bf16* W, int wp, int tk, int lane) {
-  typedef __attribute__((address_space(3))) s4v* lptr;
+__device__ __forceinline__ shortx4 tr_col(const __bf16* W, int wp, int tk, int lane) {
   const int g = lane >> 4, l16 = lane & 15;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(W + (4 * g + (l16 >> 2)) * wp + 16 * tk + 4 * (l16 & 3)));
+  return tr4(W + (4 * g + (l16 >> 2)) * wp + 16 * tk + 4 * (l16 & 3));
 }
 
 // 16x16 tile held as acc[e] = X[row 4q + e][col r] -> rows of 4 consecutive columns per lane
@@ -570,12 +554,6 @@ __device__ __forceinline__ f4 tile_rows(float* T, const f4& acc, int r, int q, i
   const f4 v = ld4(&T[(lane >> 2) * TP + 4 * (lane & 3)]);
   __builtin_amdgcn_wave_barrier();
   return v;
-}
-__device__ __forceinline__ void st4q(float* p, const f4& v) { *reinterpret_cast<f4*>(p) = v; }
-__device__ __forceinline__ void st4q(__bf16* p, const f4& v) {
-  bf4v h;
-  h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
-  *reinterpret_cast<bf4v*>(p) = h;
 }
 
 // ZB (with DROP): the keep decisions of the lane's 4 NT (query, key) elements of query tile tq are
@@ -597,14 +575,14 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(
   typedef typename std::conditional<QB, __bf16, float>::type QT;
   const QT* base = reinterpret_cast<const QT*>(qkv_) + (int64_t)b * L * ld + h * 16;
   float(*Vs)[kRowP] = Vsm[wave];
-  s4v qb[NT], kb[NT], vb[NT];
+  shortx4 qb[NT], kb[NT], vb[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) {
     const int row = t * 16 + r;
     const f4 z = {0.f, 0.f, 0.f, 0.f};
-    qb[t] = bf4(row < L ? ldq(base + (int64_t)row * ld + 4 * q) : z);
-    kb[t] = bf4(row < L ? ldq(base + (int64_t)row * ld + d + 4 * q) : z);
-    *reinterpret_cast<f4*>(&Vs[row][4 * q]) = row < L ? ldq(base + (int64_t)row * ld + 2 * d + 4 * q) : z;
+    qb[t] = bf4(row < L ? ld4(base + (int64_t)row * ld + 4 * q) : z);
+    kb[t] = bf4(row < L ? ld4(base + (int64_t)row * ld + d + 4 * q) : z);
+    *reinterpret_cast<f4*>(&Vs[row][4 * q]) = row < L ? ld4(base + (int64_t)row * ld + 2 * d + 4 * q) : z;
   }
   const uint32_t kbits = key_bits<NT>(key_pad, b, L, lane, q);
   f4 kbias[NT];
@@ -627,7 +605,7 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(
     float m = -INFINITY;
 #pragma unroll
     for (int tk = 0; tk < NT; ++tk) m = vmax(vmax(vmax(m, sv[tk][0]), sv[tk][1]), vmax(sv[tk][2], sv[tk][3]));
-    m = xmax(m);
+    m = quad_max(m);
     const float ms = m == -INFINITY ? 0.f : m * scale2;
     float l = 0.f;
     const int i = tq * 16 + r;
@@ -646,7 +624,7 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(
       }
     }
     if (ZB) zbits[((int64_t)bh * NT + tq) * 64 + lane] = (uint16_t)zw;
-    l = xsum(l);
+    l = quad_sum(l);
     f4 o = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int tk = 0; tk < NT; ++tk) o = mfma16(bf4(sv[tk]), vb[tk], o);
@@ -658,7 +636,7 @@ __global__ __launch_bounds__(256) void attn_fwd_bf16_kernel(
     for (int e = 0; e < 4; ++e) on[e] = o[e] * __shfl(rl, 4 * q + e, 64);
     const f4 v = tile_rows<kRowP>(T, on, r, q, lane);
     const int row = tq * 16 + (lane >> 2);
-    if (row < L) st4q(out + ((int64_t)b * L + row) * d + h * 16 + 4 * (lane & 3), v);
+    if (row < L) put4(out + ((int64_t)b * L + row) * d + h * 16 + 4 * (lane & 3), v);
   }
 }
 
@@ -686,7 +664,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_bf16_kernel(
   // per lane (conflict-free b64 accesses): held in registers they pushed the kernel past its
   // 168-VGPR budget (3 waves per SIMD) and the spill stores were ~56 MB of scratch writes per
   // launch at C2 (PMC WRITE_SIZE 135 MB against 79 MB of dqkv)
-  __shared__ __attribute__((aligned(16))) s4v Fsm[4][2][NT][64];
+  __shared__ __attribute__((aligned(16))) shortx4 Fsm[4][2][NT][64];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r = lane & 15, q = lane >> 4;
   const int bh = blockIdx.x * 4 + wave;
@@ -697,10 +675,10 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_bf16_kernel(
   const QT* base = reinterpret_cast<const QT*>(qkv_) + (int64_t)b * L * ld + h * 16;
   const float* gbase = dout + (int64_t)b * L * d + h * 16;
   float* T = Xsm[wave];
-  s4v qb[NT], kb[NT], vb[NT], gb[NT];
+  shortx4 qb[NT], kb[NT], vb[NT], gb[NT];
   float lsei[NT];
   // column fragments (B operands of dQ = dS K, dK = dS^T Q, dV = PZ^T dO) via the LDS image
-  s4v kc[NT];
+  shortx4 kc[NT];
   {
     f4 qf[NT], kf[NT], gf[NT];
 #pragma unroll
@@ -708,9 +686,9 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_bf16_kernel(
       const int row = t * 16 + r;
       const f4 z = {0.f, 0.f, 0.f, 0.f};
       const bool ok = row < L;
-      qf[t] = ok ? ldq(base + (int64_t)row * ld + 4 * q) : z;
-      kf[t] = ok ? ldq(base + (int64_t)row * ld + d + 4 * q) : z;
-      vb[t] = bf4(ok ? ldq(base + (int64_t)row * ld + 2 * d + 4 * q) : z);
+      qf[t] = ok ? ld4(base + (int64_t)row * ld + 4 * q) : z;
+      kf[t] = ok ? ld4(base + (int64_t)row * ld + d + 4 * q) : z;
+      vb[t] = bf4(ok ? ld4(base + (int64_t)row * ld + 2 * d + 4 * q) : z);
       gf[t] = ok ? ld4(gbase + (int64_t)row * d + 4 * q) : z;
       // base-2 log-sum-exp; +inf past L and 0 for a row with every key masked (lse = -inf): the
       // exp below then gives P = 0 for those rows as the masked selects used to
@@ -726,7 +704,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_bf16_kernel(
       if (pass == 1) {
         col_frags<NT, TP>(T, r, q, kc);
       } else {
-        s4v cf[NT];
+        shortx4 cf[NT];
         col_frags<NT, TP>(T, r, q, cf);
 #pragma unroll
         for (int t = 0; t < NT; ++t) Fsm[wave][pass >> 1][t][lane] = cf[t];
@@ -786,18 +764,18 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_bf16_kernel(
         Dp = __builtin_fmaf(pv, dpz[tk][e], Dp);
       }
       // P∘Z row slice -> W (A operand of dV = (P∘Z)^T dO after the transposed read)
-      *reinterpret_cast<s4v*>(&Wpz[r * WP + 16 * tk + 4 * q]) = bf4(pz);
+      *reinterpret_cast<shortx4*>(&Wpz[r * WP + 16 * tk + 4 * q]) = bf4(pz);
     }
     // D_i = sum_j P_ij (dP∘Z)_ij (= dO_i . O_i): from the register tiles, no O read
-    const float Di = xsum(Dp) * zs;
+    const float Di = quad_sum(Dp) * zs;
     f4 dq = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int tk = 0; tk < NT; ++tk) {
       f4 ds;
 #pragma unroll
       for (int e = 0; e < 4; ++e) ds[e] = pvs[tk][e] * __builtin_fmaf(dpz[tk][e], zs, -Di);
-      const s4v dsb = bf4(ds);
-      *reinterpret_cast<s4v*>(&Wds[r * WP + 16 * tk + 4 * q]) = dsb;
+      const shortx4 dsb = bf4(ds);
+      *reinterpret_cast<shortx4*>(&Wds[r * WP + 16 * tk + 4 * q]) = dsb;
       dq = mfma16(dsb, kc[tk], dq);  // dS[query][key] K
     }
     __builtin_amdgcn_wave_barrier();
@@ -810,7 +788,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_bf16_kernel(
     {
       const f4 v = tile_rows<TP>(T, dq * scale, r, q, lane);
       const int row = tq * 16 + (lane >> 2);
-      if (row < L) st4q(dbase + (int64_t)row * ld + 4 * (lane & 3), v);
+      if (row < L) put4(dbase + (int64_t)row * ld + 4 * (lane & 3), v);
     }
     __builtin_amdgcn_wave_barrier();
   }
@@ -821,8 +799,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_bf16_kernel(
     const f4 vv = tile_rows<TP>(T, dv_acc[tk] * zs, r, q, lane);
     const int row = tk * 16 + (lane >> 2);
     if (row < L) {
-      st4q(dbase + (int64_t)row * ld + d + 4 * (lane & 3), vk);
-      st4q(dbase + (int64_t)row * ld + 2 * d + 4 * (lane & 3), vv);
+      put4(dbase + (int64_t)row * ld + d + 4 * (lane & 3), vk);
+      put4(dbase + (int64_t)row * ld + 2 * d + 4 * (lane & 3), vv);
     }
   }
 }
@@ -864,7 +842,7 @@ __device__ __forceinline__ void load_head_image(const QT* __restrict__ base, int
   for (int e = threadIdx.x; e < LP * 4; e += 256) {
     const int row = e >> 2, c4 = (e & 3) * 4;
     f4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row < L) v = ldq(base + (int64_t)row * ld + off + c4);
+    if (row < L) v = ld4(base + (int64_t)row * ld + off + c4);
     *reinterpret_cast<f4*>(&X[row][c4]) = v;
   }
 }
@@ -905,16 +883,16 @@ __device__ __forceinline__ void load_head_image16(const QT* __restrict__ base, i
   for (int e = threadIdx.x; e < LP * 4; e += 256) {
     const int row = e >> 2, c4 = (e & 3) * 4;
     f4 v = {0.f, 0.f, 0.f, 0.f};
-    if (row < L) v = ldq(base + (int64_t)row * ld + off + c4);
-    *reinterpret_cast<s4v*>(&X[row][c4]) = bf4(v);
+    if (row < L) v = ld4(base + (int64_t)row * ld + off + c4);
+    *reinterpret_cast<shortx4*>(&X[row][c4]) = bf4(v);
   }
 }
-__device__ __forceinline__ s4v row_frag16(const __bf16 (*X)[kRowPB], int row, int q) {
-  return *reinterpret_cast<const s4v*>(&X[row][4 * q]);
+__device__ __forceinline__ shortx4 row_frag16(const __bf16 (*X)[kRowPB], int row, int q) {
+  return *reinterpret_cast<const shortx4*>(&X[row][4 * q]);
 }
 // column r, rows t0 + 4q + j of a bf16 image: the B operand fragment
-__device__ __forceinline__ s4v col_frag16(const __bf16 (*X)[kRowPB], int t0, int r, int q) {
-  s4v o;
+__device__ __forceinline__ shortx4 col_frag16(const __bf16 (*X)[kRowPB], int t0, int r, int q) {
+  shortx4 o;
 #pragma unroll
   for (int j = 0; j < 4; ++j) o[j] = __builtin_bit_cast(short, X[t0 + 4 * q + j][r]);
   return o;
@@ -954,7 +932,7 @@ __global__ __launch_bounds__(256, RS_LONG_FWD_MINW) void attn_fwd_long_bf16_kern
   __syncthreads();
   // K fragments in registers; V's column fragments re-read from the bf16 image where the P V
   // products need them (their registers kept the kernel at two waves per SIMD)
-  s4v kb[NT];
+  shortx4 kb[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t) kb[t] = row_frag16(Ks, t * 16 + r, q);
   float* T = Tsm[wave];
@@ -964,7 +942,7 @@ __global__ __launch_bounds__(256, RS_LONG_FWD_MINW) void attn_fwd_long_bf16_kern
   for (int tq = wave; tq < NTF; tq += 4) {
     const int i = tq * 16 + r;
     const f4 z = {0.f, 0.f, 0.f, 0.f};
-    const s4v qb = row_frag16(Qs, i, q);
+    const shortx4 qb = row_frag16(Qs, i, q);
     // online softmax over chunks of CH key tiles (flash-style rescale of the running sum and of
     // the P V accumulator when the max grows): only CH score tiles live at a time -- all NT of
     // them held the kernel at two waves per SIMD
@@ -984,7 +962,7 @@ __global__ __launch_bounds__(256, RS_LONG_FWD_MINW) void attn_fwd_long_bf16_kern
         sv[u] = mfma16(kb[tk], qb, ld4(&Kb[tk * 16 + 4 * q]));
         cm = vmax(vmax(vmax(cm, sv[u][0]), sv[u][1]), vmax(sv[u][2], sv[u][3]));
       }
-      cm = xmax(cm);
+      cm = quad_max(cm);
       const float mn = vmax(m, cm);
       const float msn = mn == -INFINITY ? 0.f : mn * scale2;
       if (c0 > 0) {
@@ -1012,7 +990,7 @@ __global__ __launch_bounds__(256, RS_LONG_FWD_MINW) void attn_fwd_long_bf16_kern
         o = mfma16(bf4(sv[u]), col_frag16(Vs, tk * 16, r, q), o);
       }
     }
-    l = xsum(l);
+    l = quad_sum(l);
     if (q == 0 && i < L) lse[(int64_t)bh * L + i] = (ms + __builtin_amdgcn_logf(l)) * kLn2;
     const float rl = DROP ? __builtin_amdgcn_rcpf(l) * dk.scale : __builtin_amdgcn_rcpf(l);
     f4 on;
@@ -1020,7 +998,7 @@ __global__ __launch_bounds__(256, RS_LONG_FWD_MINW) void attn_fwd_long_bf16_kern
     for (int e = 0; e < 4; ++e) on[e] = o[e] * __shfl(rl, 4 * q + e, 64);
     const f4 v = tile_rows<kRowP>(T, on, r, q, lane);
     const int row = tq * 16 + (lane >> 2);
-    if (row < L) st4q(out + ((int64_t)b * L + row) * d + h * 16 + 4 * (lane & 3), v);
+    if (row < L) put4(out + ((int64_t)b * L + row) * d + h * 16 + 4 * (lane & 3), v);
   }
   if constexpr (NR > 0) {
     // Shared query tiles (C5, L = 200: tile 12 of 13, which made wave 0 do 4 tiles against 3):
@@ -1034,7 +1012,7 @@ __global__ __launch_bounds__(256, RS_LONG_FWD_MINW) void attn_fwd_long_bf16_kern
       const int tq = NTF + x;
       const int i = tq * 16 + r;
       const f4 z = {0.f, 0.f, 0.f, 0.f};
-      const s4v qb = row_frag16(Qs, i, q);
+      const shortx4 qb = row_frag16(Qs, i, q);
       f4 sv[NT];
       float m = -INFINITY;
 #pragma unroll
@@ -1043,7 +1021,7 @@ __global__ __launch_bounds__(256, RS_LONG_FWD_MINW) void attn_fwd_long_bf16_kern
         sv[tk] = mfma16(kb[tk], qb, ld4(&Kb[tk * 16 + 4 * q]));
         m = vmax(vmax(vmax(m, sv[tk][0]), sv[tk][1]), vmax(sv[tk][2], sv[tk][3]));
       }
-      m = xmax(m);
+      m = quad_max(m);
       m = m == -INFINITY ? -INFINITY : m * scale2;  // the merge below reads -inf as "no valid key"
       const float ms = m == -INFINITY ? 0.f : m;
       float l = 0.f;
@@ -1062,7 +1040,7 @@ __global__ __launch_bounds__(256, RS_LONG_FWD_MINW) void attn_fwd_long_bf16_kern
         }
         o = mfma16(bf4(sv[tk]), col_frag16(Vs, tk * 16, r, q), o);
       }
-      l = xsum(l);
+      l = quad_sum(l);
       if (q == 0) {
         mlp[wave][x][0][r] = m;
         mlp[wave][x][1][r] = l;
@@ -1105,7 +1083,7 @@ __global__ __launch_bounds__(256, RS_LONG_FWD_MINW) void attn_fwd_long_bf16_kern
       }
       const f4 v = tile_rows<kRowP>(T, on, r, q, lane);
       const int row = tq * 16 + (lane >> 2);
-      if (row < L) st4q(out + ((int64_t)b * L + row) * d + h * 16 + 4 * (lane & 3), v);
+      if (row < L) put4(out + ((int64_t)b * L + row) * d + h * 16 + 4 * (lane & 3), v);
     }
   }
 }
@@ -1190,7 +1168,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_long1_bf16_kernel(
   QT* dbase = reinterpret_cast<QT*>(dqkv_) + (int64_t)b * L * ld + h * 16;
   __syncthreads();
 
-  s4v kr[NW], vr[NW], kc[NW];
+  shortx4 kr[NW], vr[NW], kc[NW];
   float kval[NW];
   f4 dk_acc[NW], dv_acc[NW], dq_acc[NT];
 #pragma unroll
@@ -1204,10 +1182,10 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_long1_bf16_kernel(
   }
 #pragma unroll
   for (int tq = 0; tq < NT; ++tq) {
-    const s4v qr = row_frag16(Qs, tq * 16 + r, q);
-    const s4v gr = row_frag16(Gs, tq * 16 + r, q);
-    const s4v qc[1] = {col_frag16(Qs, tq * 16, r, q)};
-    const s4v gc[1] = {col_frag16(Gs, tq * 16, r, q)};
+    const shortx4 qr = row_frag16(Qs, tq * 16 + r, q);
+    const shortx4 gr = row_frag16(Gs, tq * 16 + r, q);
+    const shortx4 qc[1] = {col_frag16(Qs, tq * 16, r, q)};
+    const shortx4 gc[1] = {col_frag16(Gs, tq * 16, r, q)};
     const f4 l2 = ld4(&L2s[tq * 16 + 4 * q]);
     const f4 Dq = ld4(&Ds[tq * 16 + 4 * q]);
     dq_acc[tq] = z;
@@ -1231,12 +1209,12 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_long1_bf16_kernel(
         ds[e] = pv * __builtin_fmaf(mk[e], pacc[e], -Dq[e]);
       }
       dv_acc[u] = mfma16(bf4(pz), gc[0], dv_acc[u]);  // (P∘Z)^T dO
-      const s4v dsb = bf4(ds);
+      const shortx4 dsb = bf4(ds);
       dk_acc[u] = mfma16(dsb, qc[0], dk_acc[u]);  // dS^T Q
       // dS with the key on the k side: Tb[u][query][key] -> lane (r, q) reads row r, keys 4q..4q+3
       // (measured: an 8-byte [key][query] row store read back with tr_col spilled at this
       // kernel's 168-VGPR budget)
-      const bf4v dh = __builtin_bit_cast(bf4v, dsb);
+      const bf16x4 dh = __builtin_bit_cast(bf16x4, dsb);
 #pragma unroll
       for (int e = 0; e < 4; ++e) Tb[u * 16 * TPB + (4 * q + e) * TPB + r] = dh[e];
     }
@@ -1244,7 +1222,7 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_long1_bf16_kernel(
 #pragma unroll
     for (int u = 0; u < NW; ++u) {
       if (u >= NW0 && (tq & 3) != wave) continue;
-      const s4v dst = *reinterpret_cast<const s4v*>(&Tb[u * 16 * TPB + r * TPB + 4 * q]);
+      const shortx4 dst = *reinterpret_cast<const shortx4*>(&Tb[u * 16 * TPB + r * TPB + 4 * q]);
       dq_acc[tq] = mfma16(dst, kc[u], dq_acc[tq]);  // dS K: [query 4q + e][c = r]
     }
     __builtin_amdgcn_wave_barrier();
@@ -1257,8 +1235,8 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_long1_bf16_kernel(
     const f4 vv = tile_rows<TP>(T, dv_acc[u], r, q, lane);
     const int row = tk * 16 + (lane >> 2);
     if (row < L) {
-      st4q(dbase + (int64_t)row * ld + d + 4 * (lane & 3), vk);
-      st4q(dbase + (int64_t)row * ld + 2 * d + 4 * (lane & 3), vv);
+      put4(dbase + (int64_t)row * ld + d + 4 * (lane & 3), vk);
+      put4(dbase + (int64_t)row * ld + 2 * d + 4 * (lane & 3), vv);
     }
   }
   // dQ partials (every query tile) and the shared key tiles' dK / dV partials summed in wave order
@@ -1292,15 +1270,15 @@ __global__ __launch_bounds__(256, 3) void attn_bwd_long1_bf16_kernel(
       const f4 vv = tile_rows<TP>(T, accs[(x * 2 + 1) * 64 + lane], r, q, lane);
       const int row = (NTF + x) * 16 + (lane >> 2);
       if (row < L) {
-        st4q(dbase + (int64_t)row * ld + d + 4 * (lane & 3), vk);
-        st4q(dbase + (int64_t)row * ld + 2 * d + 4 * (lane & 3), vv);
+        put4(dbase + (int64_t)row * ld + d + 4 * (lane & 3), vk);
+        put4(dbase + (int64_t)row * ld + 2 * d + 4 * (lane & 3), vv);
       }
     }
   }
   for (int e = threadIdx.x; e < LP * 4; e += 256) {
     const int row = e >> 2, c4 = (e & 3) * 4;
     if (row >= L) continue;
-    st4q(dbase + (int64_t)row * ld + c4, ld4(accq + row * 16 + c4) * scale);
+    put4(dbase + (int64_t)row * ld + c4, ld4(accq + row * 16 + c4) * scale);
   }
 }
 

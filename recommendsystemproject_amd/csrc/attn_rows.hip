@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma.h"
 #include "rng.h"
 
 namespace rs {
@@ -22,21 +23,11 @@ namespace {
 
 constexpr int kMaxChunks = 4;  // L <= 256
 
-__device__ __forceinline__ float wsum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float wmax(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 __device__ __forceinline__ float r16(float x) { return (float)(__bf16)x; }
 
 // Wave totals of HD per-lane channels, transposed: each butterfly step halves the channels a lane
 // carries (it keeps the half its partner does not), so HD + log2(64 / HD) - 1 shuffles replace
-// wsum's 6 HD (96 at head_dim 16). Lane l ends with the total of channel l >> RowShift<HD>.
+// wave_sum's 6 HD (96 at head_dim 16). Lane l ends with the total of channel l >> RowShift<HD>.
 template <int HD>
 struct RowShift { static constexpr int v = HD == 8 ? 3 : (HD == 16 ? 2 : (HD == 32 ? 1 : 0)); };
 template <int HD>
@@ -70,13 +61,12 @@ __device__ __forceinline__ void ldrow(const float* p, float (&x)[HD]) {
     x[c] = v.x; x[c + 1] = v.y; x[c + 2] = v.z; x[c + 3] = v.w;
   }
 }
-typedef __bf16 bf4r __attribute__((ext_vector_type(4)));
 template <int HD>
 __device__ __forceinline__ void ldrow(const __bf16* p, float (&x)[HD]) {
 #pragma unroll
   for (int c = 0; c < HD; c += 4) {
-    const bf4r v = *reinterpret_cast<const bf4r*>(p + c);
-    x[c] = (float)v[0]; x[c + 1] = (float)v[1]; x[c + 2] = (float)v[2]; x[c + 3] = (float)v[3];
+    const floatx4 v = ld4(p + c);
+    x[c] = v[0]; x[c + 1] = v[1]; x[c + 2] = v[2]; x[c + 3] = v[3];
   }
 }
 template <int HD>
@@ -88,11 +78,7 @@ __device__ __forceinline__ void strow(float* p, const float (&x)[HD]) {
 template <int HD>
 __device__ __forceinline__ void strow(__bf16* p, const float (&x)[HD]) {
 #pragma unroll
-  for (int c = 0; c < HD; c += 4) {
-    bf4r v;
-    v[0] = (__bf16)x[c]; v[1] = (__bf16)x[c + 1]; v[2] = (__bf16)x[c + 2]; v[3] = (__bf16)x[c + 3];
-    *reinterpret_cast<bf4r*>(p + c) = v;
-  }
+  for (int c = 0; c < HD; c += 4) put4(p + c, floatx4{x[c], x[c + 1], x[c + 2], x[c + 3]});
 }
 
 template <int HD, bool DROP, bool BF, bool QB>
@@ -132,7 +118,7 @@ __global__ __launch_bounds__(256) void attn_rows_fwd_kernel(
       m = fmaxf(m, s[ch]);
     }
   }
-  m = wmax(m);
+  m = wave_max(m);
   float l = 0.f, o[HD];
 #pragma unroll
   for (int c = 0; c < HD; ++c) o[c] = 0.f;
@@ -150,7 +136,7 @@ __global__ __launch_bounds__(256) void attn_rows_fwd_kernel(
       for (int c = 0; c < HD; ++c) o[c] += pz * (BF ? r16(v[c]) : v[c]);
     }
   }
-  l = wsum(l);
+  l = wave_sum(l);
   const float inv = 1.f / l;
   const float oc = wsum_t<HD>(o, lane) * inv;  // channel lane >> RowShift
   constexpr int SH = RowShift<HD>::v;
@@ -206,7 +192,7 @@ __global__ __launch_bounds__(256) void attn_rows_bwd_kernel(
     }
   }
   // D_i = sum_j P_ij dP_ij (= dO_i . O_i)
-  const float D = wsum(Dp);
+  const float D = wave_sum(Dp);
   float dq[HD];
 #pragma unroll
   for (int c = 0; c < HD; ++c) dq[c] = 0.f;

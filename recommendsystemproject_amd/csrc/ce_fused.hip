@@ -31,16 +31,10 @@
 #include <type_traits>
 
 #include "common.h"
+#include "mfma.h"
 
 namespace rs {
 namespace {
-
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-typedef short shortx8 __attribute__((ext_vector_type(8)));
 
 constexpr int kOwnW = 32;    // owned rows per wave
 constexpr int kWaves = 4;    // owned rows per workgroup: 128
@@ -72,20 +66,6 @@ struct CeArgs {
   const __bf16* strb;   // bf16 backward: the streamed rows pre-rounded to bf16 (the same bits the
                         // staging rounds to), half the bytes per tile: twice the tiles per batch
 };
-
-__device__ __forceinline__ bf16x8 cvt8(const floatx4& a, const floatx4& b) {
-  bf16x8 r;
-  r[0] = (__bf16)a[0]; r[1] = (__bf16)a[1]; r[2] = (__bf16)a[2]; r[3] = (__bf16)a[3];
-  r[4] = (__bf16)b[0]; r[5] = (__bf16)b[1]; r[6] = (__bf16)b[2]; r[7] = (__bf16)b[3];
-  return r;
-}
-
-__device__ __forceinline__ bf16x8 tr_frag(const __bf16* lo, const __bf16* hi) {
-  typedef __attribute__((address_space(3))) shortx4* lptr;
-  const shortx4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(lo));
-  const shortx4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(hi));
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
 
 // MODE 0: forward statistics (own = U, str = I)
 // MODE 1: dU (own = U, str = I; lse of the owned user)

@@ -38,6 +38,17 @@ void set_error(const char* fmt, ...);
 
 constexpr int kWave = 64;
 
+// across the four lane quads of an MFMA row (lanes l, l ^ 16, l ^ 32, l ^ 48): the partner 16
+// lanes away first, then the one 32 away
+__device__ __forceinline__ float quad_sum(float v) {
+  v += __shfl_xor(v, 16, kWave);
+  return v + __shfl_xor(v, 32, kWave);
+}
+__device__ __forceinline__ float quad_max(float v) {
+  v = fmaxf(v, __shfl_xor(v, 16, kWave));
+  return fmaxf(v, __shfl_xor(v, 32, kWave));
+}
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
@@ -77,13 +88,6 @@ inline bool getenv_flag(const char* name) {
   const char* v = getenv(name);
   return v && v[0] && !(v[0] == '0' && v[1] == 0);
 }
-
-// the same for a switch that defaults on: true iff set to exactly "0"
-inline bool getenv_flag0(const char* name) {
-  const char* v = getenv(name);
-  return v && v[0] == '0' && v[1] == 0;
-}
-
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 

@@ -26,14 +26,12 @@
 #include "common.h"
 #include "gemm_stream.h"
 #include "rng.h"
+#include "mfma.h"
 #include "stage.h"
 
 namespace rs {
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef const __attribute__((address_space(1))) floatx4* gptr4;
 
 constexpr int D = 64;      // d_model
@@ -89,25 +87,12 @@ struct FfnArgs {
 // kp(q, j) of the chunk -- the columns lane quad q owns in the two 16x16 output tiles 2c, 2c+1
 __host__ __device__ constexpr int kp(int q, int j) { return j < 4 ? 4 * q + j : 16 + 4 * q + (j - 4); }
 
-__device__ __forceinline__ bf16x8 cvt8(const floatx4& lo, const floatx4& hi) {
-  bf16x8 r;
-  r[0] = (__bf16)lo[0]; r[1] = (__bf16)lo[1]; r[2] = (__bf16)lo[2]; r[3] = (__bf16)lo[3];
-  r[4] = (__bf16)hi[0]; r[5] = (__bf16)hi[1]; r[6] = (__bf16)hi[2]; r[7] = (__bf16)hi[3];
-  return r;
-}
-
 __device__ __forceinline__ bf16x8 lds8(const __bf16* p) { return *reinterpret_cast<const bf16x8*>(p); }
 
 // column k of a 32-wide chunk -> its slot in the k-permuted image (inverse of kp)
 __host__ __device__ constexpr int kslot(int k) {
   const int kk = k & 31, c = k >> 5;
   return 32 * c + (kk < 16 ? 8 * (kk >> 2) + (kk & 3) : 8 * ((kk - 16) >> 2) + 4 + (kk & 3));
-}
-
-__device__ __forceinline__ void put4(__bf16* p, const floatx4& v) {
-  bf16x4 h;
-  h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
-  *reinterpret_cast<bf16x4*>(p) = h;
 }
 
 // x [M, D] row m, columns 16q .. 16q+15 (lane quad q) as the k-fragments of a K = 64 product
@@ -589,13 +574,6 @@ constexpr int WXP = 96;  // LDS pitch (bf16) of the [64][64] images: the 4 rows 
 constexpr int WG_F = 256;
 constexpr int WG_OUT = 2 * WG_F * D + WG_F + D;  // dW1 [F][D], dW2 [D][F], db1 [F], db2 [D]
 
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ shortx4 tr4(const __bf16* p) {
-  typedef __attribute__((address_space(3))) shortx4* lptr;
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(p));
-}
 
 __device__ __forceinline__ short bf16_bits(float v) { return __builtin_bit_cast(short, (__bf16)v); }
 

@@ -142,7 +142,7 @@ __device__ __forceinline__ void store_row(float* p, const float* v) {
   else p[0] = v[0];
 }
 
-// The optimizer step a lazy row is returned at (sparse.hip clamp_step: past the constants'
+// The optimizer step a lazy row is returned at (adam.h clamp_step: past the constants'
 // capacity the last slot is reused and the optimizer raises its overflow flag).
 __device__ __forceinline__ int lazy_target(const LazyLaunch& z) {
   const int cap = __float_as_int(z.consts[0].x);

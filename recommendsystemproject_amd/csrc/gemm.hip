@@ -11,13 +11,13 @@
 // Split-K (reductions over M = B*L for weight gradients) writes f32 partial slabs that a second
 // kernel sums in a fixed order (bitwise reproducible) and finishes with the epilogue.
 #include "common.h"
+#include "mfma.h"
 #include "gemm_stream.h"
 #include "rng.h"
 
 namespace rs {
 namespace {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int BK = 16;
 constexpr int PAD = 4;

@@ -17,6 +17,7 @@
 #include "common.h"
 #include "gemm_stream.h"
 #include "rng.h"
+#include "mfma.h"
 #include "stage.h"
 
 namespace rs {
@@ -25,8 +26,6 @@ namespace rs {
 
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 // same epilogue order as gemm.hip (see rsys_hip.h)
 __device__ __forceinline__ float epi_apply(const StreamArgs& a, int m, int n, float v,
@@ -579,10 +578,6 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(StreamArgs a, int P)
 // delivers from the row-major image (two transposed reads per fragment). The bias gradient
 // colsum(dY) is taken from the fp32 registers before rounding (per-thread partials, then a
 // fixed-order sum over the chunk's rows): it is exact fp32 as in the fp32 kernel.
-typedef short shortx4 __attribute__((ext_vector_type(4)));
-typedef short shortx8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4w __attribute__((ext_vector_type(4)));
 constexpr int WB_BK = 32;
 
 // LDS row pitch (bf16 elements) for a pad-wide image: the 4 rows of one transposed read must
@@ -600,17 +595,8 @@ constexpr int wb_gm(int tm, int tn) {
   return best;
 }
 
-__device__ __forceinline__ bf16x8w tr_frag(const __bf16* lds_lo, const __bf16* lds_hi) {
-  typedef __attribute__((address_space(3))) shortx4* lptr;
-  const shortx4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(lds_lo));
-  const shortx4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(lds_hi));
-  const shortx8 v = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8w, v);
-}
-
 // YB / XB: the operand is stored as bf16 in HBM (16-byte loads carry 8 elements and go to LDS
 // as they are); otherwise fp32 (4 elements per load, rounded to bf16 on the way to LDS)
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 template <int MO_PAD, int NO_PAD, bool YB, bool XB>
 __global__ __launch_bounds__(256) void wgrad_bf16_kernel(StreamArgs a, int rows_per_block) {
   constexpr int PY = wb_pitch(MO_PAD), PX = wb_pitch(NO_PAD);
@@ -659,9 +645,9 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(StreamArgs a, int rows_
       *reinterpret_cast<u32x4*>(dst) = v;
     } else {
       const floatx4 f = __builtin_bit_cast(floatx4, v);
-      bf16x4w h;
+      bf16x4 h;
       h[0] = (__bf16)f[0]; h[1] = (__bf16)f[1]; h[2] = (__bf16)f[2]; h[3] = (__bf16)f[3];
-      *reinterpret_cast<bf16x4w*>(dst) = h;
+      *reinterpret_cast<bf16x4*>(dst) = h;
     }
   };
   auto store_chunk = [&](int buf) {
@@ -670,7 +656,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(StreamArgs a, int rows_
       const int s = tid + i * 256;
       if (s < ysl) {
         if constexpr (YB) {
-          const bf16x8w hv = __builtin_bit_cast(bf16x8w, st[i]);
+          const bf16x8 hv = __builtin_bit_cast(bf16x8, st[i]);
 #pragma unroll
           for (int e = 0; e < 8; ++e) ysum[i < NYS ? i : 0][e] += (float)hv[e];
         } else {
@@ -713,7 +699,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(StreamArgs a, int rows_
     const __bf16* X = Xs + buf * WB_BK * PX;
 #pragma unroll
     for (int ks = 0; ks < WB_BK / 16; ++ks) {
-      bf16x8w af[TM], bfr[TN];
+      bf16x8 af[TM], bfr[TN];
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
         const int ti = wm * TM + i;
@@ -795,14 +781,6 @@ int wgrad_blocks(int Kr) {
 // compute mode; SURVEY §8d: C2 is quoted in bf16 with fp32 master weights).
 // k map of a 64-wide chunk c: lane (r, q) holds k = 64c + 16q + (0..15); MFMA 2c uses its first
 // 8, MFMA 2c+1 the next 8 -- the same permutation for both operands, so the sum is unchanged.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ bf16x8 cvt8(const floatx4& lo, const floatx4& hi) {
-  bf16x8 r;
-  r[0] = (__bf16)lo[0]; r[1] = (__bf16)lo[1]; r[2] = (__bf16)lo[2]; r[3] = (__bf16)lo[3];
-  r[4] = (__bf16)hi[0]; r[5] = (__bf16)hi[1]; r[6] = (__bf16)hi[2]; r[7] = (__bf16)hi[3];
-  return r;
-}
 
 // IO bit 0: A is bf16 storage (RS_GEMM_A_BF16; loaded as bf16x8, no conversion); bit 1: C is
 // written as bf16 (RS_GEMM_C_BF16; 8-byte stores). Either leaves every product unchanged.
@@ -827,9 +805,9 @@ __global__ __launch_bounds__(512) void rowgemm_bf16_kernel(StreamArgs a) {
   const int N = a.N;
   if (a.transB) {  // B = W[N][K]: rows n (dispatch: ldb % 4 == 0, 16-byte aligned)
     stage_batched<NTN, KK, 512>(a.B, a.ldb, [&](int n, int k, const floatx4& v) {
-      bf16x4w h;
+      bf16x4 h;
       h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
-      *reinterpret_cast<bf16x4w*>(Bs + n * KPH + k) = h;
+      *reinterpret_cast<bf16x4*>(Bs + n * KPH + k) = h;
     }, [&](int n, int k) { return k < K && n < N; });
   } else {  // B = W[K][N]: rows k
     stage_batched<KK, NTN, 512>(a.B, a.ldb, [&](int k, int n, const floatx4& v) {
@@ -953,9 +931,9 @@ __global__ __launch_bounds__(512) void rowgemm_bf16_kernel(StreamArgs a) {
           if (nl >= N) continue;  // N tail
           const floatx4 v = epi4_ct<EPI>(a, m, nl, acc[h] * a.alpha, ka, kb, biasv, auxv, cv);
           if constexpr (CBF) {
-            bf16x4w o;
+            bf16x4 o;
             o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
-            *reinterpret_cast<bf16x4w*>(reinterpret_cast<__bf16*>(a.C) + (int64_t)m * a.ldc + nl) = o;
+            *reinterpret_cast<bf16x4*>(reinterpret_cast<__bf16*>(a.C) + (int64_t)m * a.ldc + nl) = o;
           } else {
             *reinterpret_cast<floatx4*>(a.C + (int64_t)m * a.ldc + nl) = v;
           }

@@ -5,6 +5,7 @@
 // many tensors the model has. The clip coefficient stays on the device: no host sync.
 #include "common.h"
 #include "adam.h"
+#include "handoff.h"
 
 // no fma contraction: the dense and the lazy (sparse.hip) Adam must round identically
 #pragma clang fp contract(off)
@@ -87,7 +88,8 @@ __global__ __launch_bounds__(256) void sqnorm_clip_kernel(const float* __restric
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
-    __hip_atomic_store(ws + blockIdx.x, red[0] + red[1] + red[2] + red[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // not last_arriver: only this thread stores, so only it waits and takes the ticket (handoff.h)
+    st_sc1(ws + blockIdx.x, red[0] + red[1] + red[2] + red[3]);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     s_last = __hip_atomic_fetch_add(ticket, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (int)gridDim.x - 1;
   }
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(256) void sqnorm_clip_kernel(const float* __restric
   for (int q = 0; q < 4; ++q) {  // virtual thread threadIdx.x + 256 q of clip_coef_kernel
     t[q] = 0.0;
     for (int i = threadIdx.x + 256 * q; i < nb; i += 1024)
-      t[q] += __hip_atomic_load(ws + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      t[q] += ld_sc1(ws + i);
   }
   __syncthreads();  // red reused
 #pragma unroll

@@ -2,13 +2,11 @@
 // datasheet figures re-measured on the box): the HBM bandwidth of a float4 streaming copy and
 // the dense bf16 MFMA rate of back-to-back v_mfma_f32_32x32x16_bf16.
 #include "common.h"
+#include "mfma.h"
 
 namespace rs {
 namespace {
 
-typedef float floatx4 __attribute__((ext_vector_type(4)));
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // dst[i] = src[i] over n float4s, one float4 per lane and n / 256 workgroups: the shape that
 // measured best on the box (6.25 TB/s for 2 GiB, against 5.2-5.5 TB/s for grid-stride loops with

@@ -38,12 +38,6 @@ __global__ void adam_prepare_kernel(int64_t* step, float2* consts, int cap, floa
   }
 }
 
-// the step index clamped into the constants table (see adam_prepare_kernel)
-__device__ __forceinline__ int clamp_step(const float2* consts, int64_t t) {
-  const int cap = __float_as_int(consts[0].x);
-  return t < cap ? (int)t : cap - 1;
-}
-
 __global__ void flush_kernel(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                              int* __restrict__ last, int64_t V, int D,
                              const int64_t* __restrict__ step, const float2* __restrict__ consts,

@@ -6,9 +6,9 @@
 #pragma once
 #include <stdint.h>
 
-namespace rs {
+#include "mfma.h"
 
-typedef float stage_f4 __attribute__((ext_vector_type(4)));
+namespace rs {
 
 // src [ROWS][COLS] fp32 with row stride ld (16-byte aligned rows, COLS % 4 == 0) ->
 // put(row, col, float4 of columns col..col+3), NTHR threads, batches of BATCH loads per thread;
@@ -20,14 +20,14 @@ template <int ROWS, int COLS, int NTHR, int BATCH = 8, typename Put, typename Ok
 __device__ __forceinline__ void stage_batched(const float* src, int64_t ld, Put put, Ok ok = Ok()) {
   constexpr int C4 = COLS / 4, NV = ROWS * C4;
   constexpr int PER = (NV + NTHR - 1) / NTHR;
-  typedef const __attribute__((address_space(1))) stage_f4* gp;
+  typedef const __attribute__((address_space(1))) floatx4* gp;
 #pragma unroll
   for (int b0 = 0; b0 < PER; b0 += BATCH) {
-    stage_f4 v[BATCH];
+    floatx4 v[BATCH];
 #pragma unroll
     for (int i = 0; i < BATCH; ++i) {
       const int idx = threadIdx.x + NTHR * (b0 + i);
-      v[i] = stage_f4{0.f, 0.f, 0.f, 0.f};
+      v[i] = floatx4{0.f, 0.f, 0.f, 0.f};
       if (b0 + i < PER && idx < NV && ok(idx / C4, (idx % C4) * 4))
         v[i] = *(gp)(src + (int64_t)(idx / C4) * ld + (idx % C4) * 4);
     }

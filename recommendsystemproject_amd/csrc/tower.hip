@@ -32,14 +32,14 @@
 // epilogues and every stored tensor stay fp32. Statistics are reduced in fixed orders only (no
 // atomics): identical inputs give identical bits.
 #include "common.h"
+#include "handoff.h"
+#include "mfma.h"
 #include "rng.h"
 
 namespace rs {
 namespace {
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4t __attribute__((ext_vector_type(4)));
+typedef floatx4 f4;
 
 constexpr int KC = 32;     // k chunk per LDS stage
 constexpr int KMAX = 512;  // widest layer input held in the LDS column tables
@@ -116,31 +116,7 @@ struct OpT<__bf16> {
   static constexpr int PITCH = KC + 8;  // 80-byte rows: conflict-free b128 reads
 };
 
-template <typename T>
-__device__ __forceinline__ void lds_put4(T* dst, const f4& v) {
-  if constexpr (sizeof(T) == 4) {
-    *reinterpret_cast<f4*>(dst) = v;
-  } else {
-    bf16x4t h;
-    h[0] = (__bf16)v[0]; h[1] = (__bf16)v[1]; h[2] = (__bf16)v[2]; h[3] = (__bf16)v[3];
-    *reinterpret_cast<bf16x4t*>(dst) = h;
-  }
-}
-
 __device__ __forceinline__ int tile_rows(int tm, int Bg, int t) { return min(tm, Bg - t * tm); }
-
-__device__ __forceinline__ float ld_sc1(const float* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_sc1(const double* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_sc1(float* p, float v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void st_sc1(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // Workgroup barrier for LDS hand-offs only: __syncthreads() carries a workgroup release fence,
 // which on gfx950 waits for every outstanding global store (and, with stores and loads mixed,
@@ -149,20 +125,6 @@ __device__ __forceinline__ void lds_barrier() {
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
   asm volatile("" ::: "memory");
-}
-
-// One ticket per workgroup: every thread's sc1 stores drained, the workgroup's barrier, one
-// agent-scope add; returns true (uniformly) in the workgroup whose add came last.
-__device__ __forceinline__ bool ticket(int* cnt, int last) {
-  __shared__ int s_last;
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int old = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_last = old == last;
-  }
-  __syncthreads();
-  return s_last != 0;
 }
 
 // The producer side of a BatchNorm hand-off. Threads tid < ncols hold this tile's values of
@@ -181,7 +143,7 @@ __device__ __forceinline__ bool fin_publish(const Fin& f, int N, int tiles, int 
     st_sc1(pp, v0);
     st_sc1(pp + N, v1);
   }
-  return ticket(f.cnt + g * f.nb + nb, tiles - 1);
+  return last_arriver(f.cnt + g * f.nb + nb, tiles - 1);
 }
 
 // What the last arriver read-modify-writes at the very end (the running statistics, or dgamma /
@@ -362,7 +324,7 @@ __device__ __forceinline__ void fin_merge(const Fin& f, int N, int G, int Bg, in
   }
   if (tid == 0) __hip_atomic_store(f.cnt + g * f.nb + nb, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   int* cnt2 = f.cnt + G * f.nb + nb;
-  if (!ticket(cnt2, G - 1)) return;
+  if (!last_arriver(cnt2, G - 1)) return;
   // ---- every group of column block nb is in: cross-group step, groups in order
   if (tid < ncols) {
     const int col = n0 + tid;
@@ -638,7 +600,7 @@ __global__ __launch_bounds__(256) void tower_kernel(TwArgs p) {
         // every load of the workgroup was issued before the loop (D >= the chunk count) or is
         // older than these stores, so no wait for them is needed before the kernel's end
         if (hwrite && ok) *reinterpret_cast<f4*>(p.h_out + (size_t)(mbase + rl) * K + k) = v;
-        if (AR % 256 == 0 || idx < AR) lds_put4<T>(&As[buf][rl][kl], v);
+        if (AR % 256 == 0 || idx < AR) put4(&As[buf][rl][kl], v);
       }
 #pragma unroll
       for (int u = 0; u < LW; ++u) {
@@ -646,7 +608,7 @@ __global__ __launch_bounds__(256) void tower_kernel(TwArgs p) {
         if (!p.wt) {
           const int nl = idx >> 3, kl = (idx & 7) * 4;
           const bool ok = n0 + nl < N && kc * KC + kl < K;
-          lds_put4<T>(&Bs[buf][nl][kl], ok ? rw[u] : zero4);
+          put4(&Bs[buf][nl][kl], ok ? rw[u] : zero4);
         } else {
           const int kl = idx / (TN / 4), nl = (idx % (TN / 4)) * 4;
           const bool ok = kc * KC + kl < K && n0 + nl < N;
@@ -733,11 +695,11 @@ __global__ __launch_bounds__(256) void tower_kernel(TwArgs p) {
         lds_barrier();
         if (more) load(min(kc + D, nk - 1), ra[st], ra2[st], rw[st]);
         if constexpr (sizeof(T) == 2) {
-          bf16x8t af[MT], bfr[NTL];
+          bf16x8 af[MT], bfr[NTL];
 #pragma unroll
-          for (int i = 0; i < MT; ++i) af[i] = *reinterpret_cast<const bf16x8t*>(&As[buf][wrow + 16 * i + r16][q * 8]);
+          for (int i = 0; i < MT; ++i) af[i] = *reinterpret_cast<const bf16x8*>(&As[buf][wrow + 16 * i + r16][q * 8]);
 #pragma unroll
-          for (int j = 0; j < NTL; ++j) bfr[j] = *reinterpret_cast<const bf16x8t*>(&Bs[buf][wcol + 16 * j + r16][q * 8]);
+          for (int j = 0; j < NTL; ++j) bfr[j] = *reinterpret_cast<const bf16x8*>(&Bs[buf][wcol + 16 * j + r16][q * 8]);
 #pragma unroll
           for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -1066,9 +1028,6 @@ int bwd_dispatch(const TwArgs& a, hipStream_t st) {
 // s = 0..S-1 and adds the sum into dW (and db: fp32 column sums of the unrounded dz).
 // fp32 mode: the same kernel on v_mfma_f32_32x32x2_f32, chunks staged as fp32 (pitch 96 floats:
 // the two rows of a k-step fall in opposite bank halves) and read one element per lane.
-typedef short wshortx4 __attribute__((ext_vector_type(4)));
-typedef short wshortx8 __attribute__((ext_vector_type(8)));
-typedef float f16v __attribute__((ext_vector_type(16)));
 constexpr int WG_MAXJ = 4;
 constexpr int WCH = 32;         // rows per chunk
 constexpr int WPITCH = 96;      // bf16 LDS pitch of a 64-wide image (4 rows of a transposed read in distinct 64-B windows)
@@ -1086,14 +1045,6 @@ struct WgArgs {
   WgJob j[WG_MAXJ];
   int nj, M;
 };
-
-__device__ __forceinline__ bf16x8t wtr_frag(const __bf16* lo, const __bf16* hi) {
-  typedef __attribute__((address_space(3))) wshortx4* lptr;
-  const wshortx4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(lo));
-  const wshortx4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lptr)(hi));
-  const wshortx8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8t, v);
-}
 
 template <typename T>
 __global__ __launch_bounds__(256) void tower_wgrad_kernel(WgArgs a) {
@@ -1136,11 +1087,11 @@ __global__ __launch_bounds__(256) void tower_wgrad_kernel(WgArgs a) {
       const f4 x = rok && k0 + lc < K ? rx[u] : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int e = 0; e < 4; ++e) ysum[e] += y[e];
-      lds_put4<T>(&Ys[buf][row][lc], y);
-      lds_put4<T>(&Xs[buf][row][lc], x);
+      put4(&Ys[buf][row][lc], y);
+      put4(&Xs[buf][row][lc], x);
     }
   };
-  f16v acc;
+  floatx16 acc;
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] = 0.f;
   const int wm = wave >> 1, wn = wave & 1;  // 32 x 32 sub-tile of the wave: n rows wm, k cols wn
@@ -1170,8 +1121,8 @@ __global__ __launch_bounds__(256) void tower_wgrad_kernel(WgArgs a) {
         for (int ks = 0; ks < WCH / 16; ++ks) {
           const __bf16* py = &Ys[buf][16 * ks + trow][32 * wm + tcol];
           const __bf16* px = &Xs[buf][16 * ks + trow][32 * wn + tcol];
-          const bf16x8t af = wtr_frag(py, py + 4 * WPITCH);
-          const bf16x8t bf = wtr_frag(px, px + 4 * WPITCH);
+          const bf16x8 af = tr_frag(py, py + 4 * WPITCH);
+          const bf16x8 bf = tr_frag(px, px + 4 * WPITCH);
           acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, bf, acc, 0, 0, 0);
         }
       }
@@ -1193,16 +1144,16 @@ __global__ __launch_bounds__(256) void tower_wgrad_kernel(WgArgs a) {
   for (int e = 0; e < 16; ++e) st_sc1(pt + (size_t)s * 4096 + e * 256 + tid, acc[e]);
   float* pdb = J.part + (size_t)J.tn * J.tk * J.S * 4096 + ((size_t)tn * J.S) * 64;
   if (do_db && tid < 64) st_sc1(pdb + s * 64 + tid, dbv);
-  if (!ticket(J.cnt + tile, J.S - 1)) return;
+  if (!last_arriver(J.cnt + tile, J.S - 1)) return;
   // the S partials (this workgroup's own included: its sc1 stores are drained) summed in split
   // order, 4 splits' loads in flight at a time: one split per round trip made the last arriver's
   // tail ~S x 1.5 us
-  f16v sum;
+  floatx16 sum;
 #pragma unroll
   for (int e = 0; e < 16; ++e) sum[e] = 0.f;
   constexpr int QB = 4;
   for (int q0 = 0; q0 < J.S; q0 += QB) {
-    f16v v[QB];
+    floatx16 v[QB];
 #pragma unroll
     for (int u = 0; u < QB; ++u) {
       const int q = min(q0 + u, J.S - 1);
