@@ -249,6 +249,15 @@ int rs_ffn_wgrad_bf16(int M, int F, const float* x, const float* W1, const float
 int rs_wgrad_bf16(int rows, int Mo, int No, const void* dy, int ldy, int dy_bf16, const void* x,
                   int ldx, int x_bf16, float beta, float* dW, int ldw, float* db, float* ws,
                   void* stream);
+/* The in-projection's whole backward from ONE read of dy = dqkv [M, N = 192] (bf16 storage,
+ * contiguous), bf16 mode: dW[N][K] += dy^T x, db += colsum(dy), dx[M][K = 64] = dy W (+ dx_in when
+ * given; dx_in may be dx itself). x [M, K] and dx contiguous fp32, W [N][ldw], dW contiguous.
+ * Replaces rs_wgrad_bf16 + the input-gradient GEMM of nn.MultiheadAttention's in_proj
+ * (SequenceEncoder.py:17-29), which streamed dqkv twice. Deterministic; the reduction defers under
+ * rs_reduce_defer. ws: rs_linear_bwd_bf16_ws_bytes (0: shape not covered). */
+int64_t rs_linear_bwd_bf16_ws_bytes(int M, int N, int K);
+int rs_linear_bwd_bf16(const void* dy, const float* x, const float* W, int ldw, int M, int N, int K,
+                       const float* dx_in, float* dx, float* dW, float* db, float* ws, void* stream);
 
 /* ---------------------------------------------------------------- sequence mask
  * padding mask from the first sequence feature (== pad_value) with the all-padding-row fix,
@@ -714,16 +723,36 @@ int64_t rs_seq_input_dropout_bwd_ws_bytes(int rows, int N);
 int rs_seq_input_dropout_bwd(float* dx, int rows, int N, float p, const int64_t* key, int site_a,
                              int site_b, float* pos_grad, float* ws, void* stream);
 int rs_dropout_bwd(float* dx, int64_t n, float p, const int64_t* key, int site, void* stream);
+/* The backward of SequenceFeatureProcessor's input stage (SequenceFeatureProcessor.py:77-83,
+ * x = drop_b(drop_a(cat W^T + b) + pos[l])) in the bf16 compute mode, dx [M, d] only read:
+ * rs_seq_input_bwd_bf16, ONE pass over the token rows: y = dx * mask_b * mask_a, db += colsum(y)
+ * (fp32), dW[d][dcat] += y^T cat and dcat_out[M][dcat] = y W on bf16 MFMA (fp32 accumulation).
+ * Replaces rs_seq_input_dropout_bwd's write-back and the projection's weight-gradient and
+ * input-gradient GEMMs (three streams over dx) and gives their bits. d == 64, dcat a multiple of 8
+ * up to 96 (rs_seq_input_bwd_bf16_supported); dW contiguous [d][dcat]. ws:
+ * rs_seq_input_bwd_bf16_ws_bytes.
+ * rs_seq_input_pos_grad: pos_grad[n] += sum over rows of dx * mask_b for dx [rows, N = L*d]
+ * (p == 0: of dx), any N % 4 == 0; rs_seq_input_dropout_bwd's sums without its write of dx. ws:
+ * rs_seq_input_dropout_bwd_ws_bytes.
+ * Both deterministic; the gradients' reductions defer under rs_reduce_defer. */
+int rs_seq_input_bwd_bf16_supported(int M, int d, int dcat);
+int64_t rs_seq_input_bwd_bf16_ws_bytes(int M, int d, int dcat);
+int rs_seq_input_bwd_bf16(const float* dx, const float* cat, int ldcat, const float* W, int ldw, int M,
+                          int d, int dcat, float p, const int64_t* key, int site_a, int site_b,
+                          float* dcat_out, float* dW, float* db, float* ws, void* stream);
+int rs_seq_input_pos_grad(const float* dx, int rows, int N, float p, const int64_t* key, int site_b,
+                          float* pos_grad, float* ws, void* stream);
 
 /* ---------------------------------------------------------------- reductions */
 /* Deferred parameter-gradient reductions (round 5; no reference counterpart -- the optimizer step
  * of training_utils.py:28-60 is the only reader of these gradients). After rs_reduce_defer(1) the
  * weight-gradient entry points (rs_gemm_f32's transposed-A weight gradients, rs_wgrad_bf16,
- * rs_ffn_wgrad_bf16), the fused FFN backward's LayerNorm partials and rs_seq_input_dropout_bwd's
- * positional partials queue their final split reduction instead of launching it; rs_reduce_flush
- * runs every queued reduction in one launch on `stream` (the bits of the immediate path) and
- * rs_reduce_defer(0) ends the queueing. The caller keeps each call's workspace alive until the
- * flush is queued, and reads none of those gradients before it. */
+ * rs_ffn_wgrad_bf16, rs_seq_input_bwd_bf16, rs_linear_bwd_bf16), the fused FFN backward's
+ * LayerNorm partials and rs_seq_input_dropout_bwd's / rs_seq_input_pos_grad's positional partials
+ * queue their final split reduction instead of launching it; rs_reduce_flush runs every queued
+ * reduction in one launch on `stream` (the bits of the immediate path) and rs_reduce_defer(0) ends
+ * the queueing. The caller keeps each call's workspace alive until the flush is queued, and reads
+ * none of those gradients before it. */
 int rs_reduce_defer(int on);
 int rs_reduce_flush(void* stream);
 /* out = scale * sum(x[0..n)) (deterministic; mean loss) */

@@ -71,6 +71,8 @@ SIGNATURES = {
     'rs_ffn_wgrad_ws_bytes': (i64, [i32, i32]),
     'rs_ffn_wgrad_bf16': (i32, [i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]),
     'rs_wgrad_bf16': (i32, [i32, i32, i32, vp, i32, i32, vp, i32, i32, f32, vp, i32, vp, vp, vp]),
+    'rs_linear_bwd_bf16_ws_bytes': (i64, [i32, i32, i32]),
+    'rs_linear_bwd_bf16': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
     'rs_colsum_ws_bytes': (i64, [i32, i32]),
     'rs_colsum': (i32, [vp, i32, i32, i32, f32, f32, vp, vp, vp]),
     'rs_gather_fwd': (i32, [vp, i32, i32, vp, i32, vp, vp]),
@@ -179,6 +181,11 @@ SIGNATURES = {
     'rs_dropout_fwd': (i32, [vp, i64, i32, vp, i32, i32, f32, vp, i32, vp]),
     'rs_seq_input_dropout_bwd_ws_bytes': (i64, [i32, i32]),
     'rs_seq_input_dropout_bwd': (i32, [vp, i32, i32, f32, vp, i32, i32, vp, vp, vp]),
+    'rs_seq_input_bwd_bf16_supported': (i32, [i32, i32, i32]),
+    'rs_seq_input_bwd_bf16_ws_bytes': (i64, [i32, i32, i32]),
+    'rs_seq_input_bwd_bf16': (i32, [vp, vp, i32, vp, i32, i32, i32, i32, f32, vp, i32, i32, vp, vp, vp, vp,
+                                    vp]),
+    'rs_seq_input_pos_grad': (i32, [vp, i32, i32, f32, vp, i32, vp, vp, vp]),
     'rs_dropout_bwd': (i32, [vp, i64, f32, vp, i32, vp]),
 }
 

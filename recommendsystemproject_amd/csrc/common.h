@@ -76,6 +76,9 @@ int partials_reduce2(const float* ws, int P, int N, int split, float scale, floa
 bool reduce_deferring();
 void reduce_defer_job(const float* ws, int P, int N, int nr, float* const* outs, const int* begins,
                       const float* alphas, const float* betas);
+// a job of up to 4 column ranges {out, begin, alpha, beta}: queued while deferring, else launched now
+int reduce_job(const float* ws, int P, int N, int nr, float* const* outs, const int* begins,
+               const float* alphas, const float* betas, hipStream_t st);
 int partials_reduce_any(const float* ws, int P, int N, int split, float scale, float beta, float* out0,
                         float* out1, hipStream_t st);
 // two partials_reduce2 jobs of one shape (ws0 -> a0 | a1, ws1 -> b0 | b1) in one launch

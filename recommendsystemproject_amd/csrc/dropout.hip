@@ -101,6 +101,65 @@ __global__ __launch_bounds__(256) void seq_input_dropout_bwd_kernel(float* __res
   }
 }
 
+// The positional-embedding gradient alone: pos_grad[n] += sum over rows of dx * mask_b, dx only
+// read (the bf16 mode's one-pass sequence-input backward, linear_bwd.hip, takes the rest from its
+// own read of dx). Rows, per-thread sums and partials are seq_input_dropout_bwd_kernel's, so the
+// sums carry its bits; blockIdx.y steps over column tiles of 4 * 4 * 256 (any N), p == 0 draws
+// nothing.
+__global__ __launch_bounds__(256) void seq_input_pos_grad_kernel(const float* __restrict__ dx, int rows, int N,
+                                                                 int rows_per_block, float p,
+                                                                 const int64_t* __restrict__ key, int site_b,
+                                                                 float* __restrict__ ws) {
+  const bool drop = p > 0.f;
+  DropKey kb{};
+  if (drop) kb = make_key(key, site_b, p);
+  const int G4 = N / 4;
+  const int g0 = blockIdx.y * (256 * kSeqDropCols);
+  const int r0 = blockIdx.x * rows_per_block;
+  const int r1 = min(rows, r0 + rows_per_block);
+  float4 acc[kSeqDropCols];
+#pragma unroll
+  for (int u = 0; u < kSeqDropCols; ++u) acc[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 nx[kSeqDropCols];
+  if (r0 >= r1) return;
+  // (unconditional loads, row and column clamped, one row in flight behind the other: as above)
+#pragma unroll
+  for (int u = 0; u < kSeqDropCols; ++u) {
+    const int g = min(g0 + (int)threadIdx.x + 256 * u, G4 - 1);
+    nx[u] = *reinterpret_cast<const float4*>(dx + (int64_t)r0 * N + 4 * g);
+  }
+  for (int row = r0; row < r1; ++row) {
+    float4 v[kSeqDropCols];
+#pragma unroll
+    for (int u = 0; u < kSeqDropCols; ++u) v[u] = nx[u];
+    const int rn = min(row + 1, r1 - 1);
+#pragma unroll
+    for (int u = 0; u < kSeqDropCols; ++u) {
+      const int g = min(g0 + (int)threadIdx.x + 256 * u, G4 - 1);
+      nx[u] = *reinterpret_cast<const float4*>(dx + (int64_t)rn * N + 4 * g);
+    }
+#pragma unroll
+    for (int u = 0; u < kSeqDropCols; ++u) {
+      const int g = g0 + threadIdx.x + 256 * u;
+      if (g >= G4) continue;
+      float mb[4] = {1.f, 1.f, 1.f, 1.f};
+      if (drop) keep4(kb, (uint64_t)row * N + 4 * g, mb);
+      // one rounding per add, spelled out: the kernel above is compiled to this fma (its product
+      // and sum contract), and the two must agree to the bit
+      const float4 t = v[u];
+      acc[u].x = __builtin_fmaf(t.x, mb[0], acc[u].x);
+      acc[u].y = __builtin_fmaf(t.y, mb[1], acc[u].y);
+      acc[u].z = __builtin_fmaf(t.z, mb[2], acc[u].z);
+      acc[u].w = __builtin_fmaf(t.w, mb[3], acc[u].w);
+    }
+  }
+#pragma unroll
+  for (int u = 0; u < kSeqDropCols; ++u) {
+    const int g = g0 + threadIdx.x + 256 * u;
+    if (g < G4) *reinterpret_cast<float4*>(ws + (int64_t)blockIdx.x * N + 4 * g) = acc[u];
+  }
+}
+
 int seq_drop_blocks(int rows) {
   int b = cdiv(rows, 8);  // >= 8 rows per workgroup
   return b > 512 ? 512 : (b < 1 ? 1 : b);
@@ -150,6 +209,21 @@ extern "C" int rs_seq_input_dropout_bwd(float* dx, int rows, int N, float p, con
   hipStream_t st = as_stream(stream);
   seq_input_dropout_bwd_kernel<<<cdiv(rows, rpb), 256, 0, st>>>(dx, rows, N, rpb, p, key, site_a, site_b, ws);
   RS_CHECK_LAUNCH("rs_seq_input_dropout_bwd");
+  return partials_reduce_any(ws, cdiv(rows, rpb), N, N, 1.f, 1.f, pos_grad, nullptr, st);
+}
+
+extern "C" int rs_seq_input_pos_grad(const float* dx, int rows, int N, float p, const int64_t* key, int site_b,
+                                     float* pos_grad, float* ws, void* stream) {
+  RS_CHECK_ARG(dx && pos_grad && ws && rows >= 0 && N > 0 && N % 4 == 0 && p >= 0.f && p < 1.f &&
+                   (p == 0.f || key) && aligned16(dx) && aligned16(ws),
+               "rs_seq_input_pos_grad: bad args (N=%d)", N);
+  if (rows == 0) return 0;
+  const int nb = seq_drop_blocks(rows);
+  const int rpb = cdiv(rows, nb);
+  hipStream_t st = as_stream(stream);
+  seq_input_pos_grad_kernel<<<dim3(cdiv(rows, rpb), cdiv(N / 4, 256 * kSeqDropCols)), 256, 0, st>>>(
+      dx, rows, N, rpb, p, key, site_b, ws);
+  RS_CHECK_LAUNCH("rs_seq_input_pos_grad");
   return partials_reduce_any(ws, cdiv(rows, rpb), N, N, 1.f, 1.f, pos_grad, nullptr, st);
 }
 

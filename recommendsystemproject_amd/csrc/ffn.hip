@@ -17,7 +17,9 @@
 //   rebuilds f1 from the bits (no dropout hash in the backward), writes f1 and
 //   dPre1 = (dff W2) * mask / (1 - p) as bf16 for the two weight gradients, and accumulates
 //   dx1 += dPre1 W1 -- three products per row group, f1 / dPre1 never read back.
-// Weight gradients: rs_wgrad_bf16 with the bf16 operands (gemm_stream.hip).
+// Weight gradients: rs_wgrad_bf16 with the bf16 operands (gemm_stream.hip). (The in-projection's
+// weight gradient from the bf16 dqkv also came through rs_wgrad_bf16; it is now part of
+// rs_linear_bwd_bf16, linear_bwd.hip, with rs_wgrad_bf16 as the fallback.)
 //
 // Numerics are those of the bf16 compute mode (operands rounded to bf16, fp32 accumulation,
 // fp32 epilogues): identical element values to the unfused bf16 path except for the summation

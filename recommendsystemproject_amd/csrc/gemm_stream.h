@@ -47,4 +47,22 @@ int wgrad_launch(const StreamArgs& s, hipStream_t st);
 // bf16 MFMA weight gradient; y_bf16 / x_bf16: dY (A) / X (B) are stored as bf16
 int wgrad_bf16_launch(const StreamArgs& s, bool y_bf16, bool x_bf16, hipStream_t st);
 
+// bf16 weight-gradient geometry (wgrad_bf16_kernel, and linear_bwd.hip's fused backward)
+constexpr int WB_BK = 32;  // rows per staged chunk
+
+// LDS row pitch (bf16 elements) for a pad-wide image: the 4 rows of one transposed read must
+// fall in distinct 64-byte windows of the 256-byte bank space -> pitch*2 mod 256 in {64, 192}
+constexpr int wb_pitch(int pad) { return (pad % 128 == 32 || pad % 128 == 96) ? pad : pad + 32; }
+
+// wave grid over the (MO/32) x (NO/32) tiles: the split of 4 waves with the fewest fragments
+constexpr int wb_gm(int tm, int tn) {
+  int best = 1, cost = 1 << 30;
+  for (int gm = 1; gm <= 4; gm *= 2) {
+    const int gn = 4 / gm;
+    const int c = (tm + gm - 1) / gm + (tn + gn - 1) / gn + 64 * ((tm < gm) + (tn < gn));
+    if (c < cost) { cost = c; best = gm; }
+  }
+  return best;
+}
+
 }  // namespace rs

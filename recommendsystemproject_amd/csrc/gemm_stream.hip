@@ -14,6 +14,13 @@
 //   tile (Mo*No <= 16K floats in accumulators) for a chunk of rows; dY and X chunks are staged
 //   k-major exactly as they lie in memory (no transposition), partial tiles are summed by a
 //   fixed-order reduce (deterministic), and the bias gradient colsum(dY) is fused.
+// In the bf16 mode two backward pairs of these kernels are replaced by one-pass kernels in
+// linear_bwd.hip, which share wgrad_bf16_kernel's chunk geometry (gemm_stream.h) and row split
+// and rowgemm_bf16_kernel's k map, and so give these kernels' bits: the sequence projection's
+// (dropout backward + wgrad_bf16<64, 64> + the input-gradient rowgemm -> rs_seq_input_bwd_bf16,
+// beside rs_seq_input_pos_grad's read-only pass for the positional gradient) and the in-projection's on a bf16 dqkv (wgrad_bf16<192, 64, true, false>
+// + rowgemm_bf16<4, 3, ..., 1> -> rs_linear_bwd_bf16). The pairs here remain their fallbacks
+// (RSYS_SEQ_BWD_FUSED=0 / RSYS_LINBWD_FUSED=0, unsupported shapes) and the fp32 mode's path.
 #include "common.h"
 #include "gemm_stream.h"
 #include "rng.h"
@@ -578,22 +585,7 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(StreamArgs a, int P)
 // delivers from the row-major image (two transposed reads per fragment). The bias gradient
 // colsum(dY) is taken from the fp32 registers before rounding (per-thread partials, then a
 // fixed-order sum over the chunk's rows): it is exact fp32 as in the fp32 kernel.
-constexpr int WB_BK = 32;
-
-// LDS row pitch (bf16 elements) for a pad-wide image: the 4 rows of one transposed read must
-// fall in distinct 64-byte windows of the 256-byte bank space -> pitch*2 mod 256 in {64, 192}
-constexpr int wb_pitch(int pad) { return (pad % 128 == 32 || pad % 128 == 96) ? pad : pad + 32; }
-
-// wave grid over the (MO/32) x (NO/32) tiles: the split of 4 waves with the fewest fragments
-constexpr int wb_gm(int tm, int tn) {
-  int best = 1, cost = 1 << 30;
-  for (int gm = 1; gm <= 4; gm *= 2) {
-    const int gn = 4 / gm;
-    const int c = (tm + gm - 1) / gm + (tn + gn - 1) / gn + 64 * ((tm < gm) + (tn < gn));
-    if (c < cost) { cost = c; best = gm; }
-  }
-  return best;
-}
+// WB_BK, wb_pitch, wb_gm: gemm_stream.h (shared with linear_bwd.hip)
 
 // YB / XB: the operand is stored as bf16 in HBM (16-byte loads carry 8 elements and go to LDS
 // as they are); otherwise fp32 (4 elements per load, rounded to bf16 on the way to LDS)

@@ -268,6 +268,20 @@ void reduce_defer_job(const float* ws, int P, int N, int nr, float* const* outs,
   g_jobs.push_back(j);
 }
 
+// one job with up to 4 column ranges: queued while deferring, else launched at once -- the same
+// kernel either way, so both paths give the same bits
+int reduce_job(const float* ws, int P, int N, int nr, float* const* outs, const int* begins,
+               const float* alphas, const float* betas, hipStream_t st) {
+  if (g_defer) {
+    reduce_defer_job(ws, P, N, nr, outs, begins, alphas, betas);
+    return 0;
+  }
+  RedJob j{};
+  j.ws = ws; j.P = P; j.N = N; j.nr = nr;
+  for (int i = 0; i < nr; ++i) j.r[i] = JobRange{outs[i], begins[i], alphas[i], betas[i]};
+  return launch_jobs(&j, 1, st);
+}
+
 }  // namespace rs
 
 extern "C" int rs_reduce_defer(int on) {

@@ -313,12 +313,18 @@ def seq_input_fwd(proc, seqd, B, L, p, key, err, need=True):
     return x, (segs, tables, cat, keep, calls)
 
 
-def seq_input_bwd(proc, saved, dx, B, L, p, key, params=()):
-    """Backward of seq_input_fwd; dx [B*L, d] is consumed (modified in place). `params`: the
-    calling op's parameters (its data-parallel bucket, dist.GradBuckets)."""
-    segs, tables, cat, _, calls = saved
-    d = proc.target_dim
-    pos_g = grad_of(proc.pos_emb.weight)
+def seq_input_grads(dx, cat, W, B, L, p, key, dW, db, pos_g, consume=True):
+    """Gradients of x = drop_b(drop_a(cat W^T + b) + pos[l]) from dx [B*L, d]: dW += y^T cat,
+    db += colsum(y), pos_g[:L] += the sum over samples of dx * mask_b; returns dcat = y W
+    (y = dx * mask_b * mask_a; sites 0, 1). bf16 mode, a supported shape: two kernels that only
+    read dx, one for pos_g and one for the rest (csrc/dropout.hip, csrc/linear_bwd.hip;
+    RSYS_SEQ_BWD_FUSED=0 turns them off; the same bits as the unfused streaming kernels). Otherwise the dropout backward
+    runs in place over dx (over a copy unless `consume`), then the two GEMMs."""
+    d = dx.shape[1]
+    if ops.seq_input_bwd_fused_ok(dx, cat, W, dW, L):
+        return ops.seq_input_bwd_fused(dx, cat, W, L, p, key, 0, 1, dW, db, pos_g)
+    if not consume:
+        dx = dx.clone()
     if p > 0 and (L * d) % 4 == 0 and L * d <= 4096:
         # drop_b backward, d pos_emb[l] = sum_b dx[b, l], drop_a backward: one pass
         ops.seq_input_dropout_bwd(dx, pos_g, B, L * d, p, key, 0, 1)
@@ -328,10 +334,19 @@ def seq_input_bwd(proc, saved, dx, B, L, p, key, params=()):
         ops.colsum(dx, pos_g, M=B, N=L * d, ldx=L * d)  # d pos_emb[l] = sum_b dx[b, l]
         if p > 0:
             ops.dropout_bwd(dx, p, key, 0)
-    lin = proc.feature_projection[0]
     # dx is final here (the dropout backward above ran in place before this point)
-    ops.linear_bwd_weight(dx, cat, grad_of(lin.weight), db=grad_of(lin.bias))
-    dcat = ops.linear_bwd_input(dx, lin.weight)
+    ops.linear_bwd_weight(dx, cat, dW, db=db)
+    return ops.linear_bwd_input(dx, W)
+
+
+def seq_input_bwd(proc, saved, dx, B, L, p, key, params=(), consume=True):
+    """Backward of seq_input_fwd; dx [B*L, d] is consumed (modified in place on the unfused path)
+    unless `consume` is false. `params`: the calling op's parameters (its data-parallel bucket,
+    dist.GradBuckets)."""
+    segs, tables, cat, _, calls = saved
+    lin = proc.feature_projection[0]
+    dcat = seq_input_grads(dx, cat, lin.weight, B, L, p, key, grad_of(lin.weight), grad_of(lin.bias),
+                           grad_of(proc.pos_emb.weight), consume)
     for s, t in zip(segs, tables):
         s.grad = grad_of(t).data_ptr()
     _grad_tables(segs, calls, dcat, tables, B * L, params)
@@ -360,8 +375,9 @@ class SeqFeaturesFn(torch.autograd.Function):
     @staticmethod
     @once_differentiable
     def backward(ctx, dx):
-        dx = dx.contiguous().view(ctx.B * ctx.L, -1).clone()  # consumed in place below
-        seq_input_bwd(ctx.proc, ctx.saved, dx, ctx.B, ctx.L, ctx.p, ctx.key, ctx.params)
+        dx = dx.contiguous().view(ctx.B * ctx.L, -1)
+        # autograd's buffer: the fused kernels only read it, the unfused path works on a copy
+        seq_input_bwd(ctx.proc, ctx.saved, dx, ctx.B, ctx.L, ctx.p, ctx.key, ctx.params, consume=False)
         ctx.saved = ctx.params = None
         return (None, None, None) + (None,) * (len(ctx.needs_input_grad) - 3)
 
@@ -479,6 +495,10 @@ def _in_proj_bwd(lyr, x, dqkv, dx=None):
     """in_proj weight gradient and dx (+)= dqkv W_in."""
     g = grad_of
     sa_mod = lyr.self_attn
+    if ops.linear_bwd_fused_ok(dqkv, x, sa_mod.in_proj_weight, g(sa_mod.in_proj_weight), dx):
+        # bf16 dqkv: weight / bias gradients and dx from one read of it (csrc/linear_bwd.hip)
+        return ops.linear_bwd_fused(dqkv, x, sa_mod.in_proj_weight, g(sa_mod.in_proj_weight),
+                                    g(sa_mod.in_proj_bias), dx_in=dx)
     if dqkv.dtype == torch.bfloat16:  # bf16 dqkv (RS_ATTN_QKV_BF16): bf16-MFMA weight gradient
         ops.wgrad_bf16(dqkv, x, g(sa_mod.in_proj_weight), db=g(sa_mod.in_proj_bias))
     else:

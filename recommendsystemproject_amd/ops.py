@@ -216,6 +216,40 @@ def wgrad_bf16(dy, x, dW, *, db=None, beta=1.0):
     return dW
 
 
+def _aligned16(*tensors):
+    """The 16-byte alignment the one-pass kernels' vector loads need (their entry points check it):
+    a view that lacks it takes the unfused path."""
+    return all(t.data_ptr() % 16 == 0 for t in tensors)
+
+
+def linear_bwd_fused_ok(dy, x, W, dW, dx_in=None):
+    """The one-pass Linear backward for a bf16-stored dy (csrc/linear_bwd.hip: the in-projection's
+    [M, 192] x [192, 64]): bf16 compute mode, a covered shape, and RSYS_LINBWD_FUSED not 0."""
+    if precision.compute_dtype() != 'bf16' or os.environ.get('RSYS_LINBWD_FUSED', '1') == '0':
+        return False
+    M, N = dy.shape
+    K = x.shape[1]
+    return (dy.dtype == torch.bfloat16 and x.dtype == torch.float32 and dy.is_contiguous() and
+            x.is_contiguous() and tuple(W.shape) == (N, K) and W.stride(1) == 1 and W.stride(0) % 4 == 0 and
+            dW.is_contiguous() and _aligned16(dy, x, W) and
+            (dx_in is None or (dx_in.is_contiguous() and tuple(dx_in.shape) == (M, K) and _aligned16(dx_in))) and
+            _hip.lib().rs_linear_bwd_bf16_ws_bytes(M, N, K) > 0)
+
+
+def linear_bwd_fused(dy, x, W, dW, db, dx_in=None):
+    """dW += dy^T x, db += colsum(dy), returns dx = dy W (+ dx_in, written over dx_in) from one read
+    of dy (rs_linear_bwd_bf16)."""
+    M, N = dy.shape
+    K = x.shape[1]
+    if dx_in is not None and not (dx_in.is_contiguous() and tuple(dx_in.shape) == (M, K)):
+        raise RuntimeError('linear_bwd_fused: dx_in must be a contiguous [M, K] tensor')
+    dx = dx_in if dx_in is not None else torch.empty(M, K, device=dy.device, dtype=torch.float32)
+    w = ws(_hip.lib().rs_linear_bwd_bf16_ws_bytes(M, N, K), dy.device)
+    call('rs_linear_bwd_bf16', P(dy), P(x), P(W), W.stride(0), M, N, K, P(dx_in), P(dx), P(dW), P(db), P(w),
+         stream())
+    return dx
+
+
 def colsum(X, out, *, scale=1.0, beta=1.0, M=None, N=None, ldx=None):
     """out[n] = beta*out[n] + scale*sum_m X[m, n]."""
     if M is None:
@@ -435,6 +469,35 @@ def seq_input_dropout_bwd(dx, pos_grad, rows, N, p, key, site_a, site_b):
     call('rs_seq_input_dropout_bwd', P(dx), rows, N, float(p), P(key), site_a, site_b, P(pos_grad), P(w),
          stream())
     return dx
+
+
+def seq_input_bwd_fused_ok(dx, cat, W, dW, L):
+    """The one-pass sequence-input backward (csrc/linear_bwd.hip): bf16 compute mode, a supported
+    shape, and RSYS_SEQ_BWD_FUSED not 0."""
+    if precision.compute_dtype() != 'bf16' or os.environ.get('RSYS_SEQ_BWD_FUSED', '1') == '0':
+        return False
+    M, d = dx.shape
+    dcat = cat.shape[1]
+    return (dx.is_contiguous() and dx.dtype == torch.float32 and cat.dtype == torch.float32 and
+            cat.stride(1) == 1 and cat.stride(0) % 4 == 0 and tuple(W.shape) == (d, dcat) and W.stride(1) == 1 and
+            dW.is_contiguous() and _aligned16(dx, cat) and L >= 1 and M % L == 0 and (L * d) % 4 == 0 and
+            bool(_hip.lib().rs_seq_input_bwd_bf16_supported(M, d, dcat)))
+
+
+def seq_input_bwd_fused(dx, cat, W, L, p, key, site_a, site_b, dW, db, pos_grad):
+    """dcat = (dx * mask_b * mask_a) W; dW += y^T cat, db += colsum(y) in one pass
+    (rs_seq_input_bwd_bf16), and pos_grad[:L] += the sum over samples of dx * mask_b
+    (rs_seq_input_pos_grad); dx is only read. Returns dcat."""
+    M, d = dx.shape
+    dcat = cat.shape[1]
+    k = P(key) if p > 0 else None
+    w = ws(_hip.lib().rs_seq_input_dropout_bwd_ws_bytes(M // L, L * d), dx.device)
+    call('rs_seq_input_pos_grad', P(dx), M // L, L * d, float(p), k, site_b, P(pos_grad), P(w), stream())
+    out = torch.empty(M, dcat, device=dx.device, dtype=torch.float32)
+    w = ws(_hip.lib().rs_seq_input_bwd_bf16_ws_bytes(M, d, dcat), dx.device)
+    call('rs_seq_input_bwd_bf16', P(dx), P(cat), cat.stride(0), P(W), W.stride(0), M, d, dcat, float(p), k,
+         site_a, site_b, P(out), P(dW), P(db), P(w), stream())
+    return out
 
 
 def dropout_bwd(dx, p, key, site):

@@ -192,6 +192,13 @@ WORK = {
     'rs_ffn_fwd_bf16': _ffn_fwd_work,
     'rs_ffn_bwd_bf16': _ffn_bwd_work,
     'rs_wgrad_bf16': _wgrad_work,
+    # one pass: dy (bf16) and x read, dx written (+ read with a residual); dW = dy^T x and dx = dy W
+    'rs_linear_bwd_bf16': lambda a: (4.0 * a[4] * a[5] * a[6],
+                                     a[4] * (2.0 * a[5] + 4.0 * a[6] * (3 if a[7] else 2))),
+    # one pass: dx read, cat read, dcat written; dW = y^T cat and dcat = y W
+    'rs_seq_input_bwd_bf16': lambda a: (4.0 * a[5] * a[6] * a[7], 4.0 * a[5] * (a[6] + 2 * a[7])),
+    # its companion's second read of dx [rows, N] (one fma per element; the partials are small)
+    'rs_seq_input_pos_grad': lambda a: (2.0 * a[1] * a[2], 4.0 * a[1] * a[2]),
     'rs_inbatch_ce_fwd': _ce_work,
     'rs_inbatch_ce_bwd': lambda a: _ce_work(a, True),
     'rs_gemm_f32': _gemm_work,
