@@ -516,6 +516,32 @@ int rs_topk_rows(const float* S, int64_t ld, int B, int N, int K, const int32_t*
 int rs_recall_hits(const int32_t* topk_idx, int B, int K, const int64_t* item_ids,
                    const int64_t* targets, int64_t target_stride, const int32_t* ks, int nk,
                    int32_t* hits, void* stream);
+/* The same retrieval without the score matrix (csrc/retrieve.hip; serving, validate(retrieval=
+ * 'fused')): rs_fused_topk gives, for users U [B, D] fp32 (row stride ldu) and an item matrix
+ * [N, D] (fp32, or bf16 with items_bf16; row stride ldi in elements), the K best catalog columns
+ * of every user by dot product and their scores -- what rs_gemm_f32 + rs_mask_history +
+ * rs_topk_rows define: values descending, ties by the lower column; a column of the user's
+ * history CSR (hist_off / hist_idx as rs_mask_history's, but each user's slice SORTED ascending)
+ * scores -inf and appears only when fewer than K others exist, lowest column first. user_ids
+ * outside [0, num_users) or NULL user_ids / hist_off / hist_idx: no exclusion. fp32 items: exact
+ * f32 products (v_mfma_f32_32x32x2_f32); bf16 items: U rounded to bf16 (RNE) in the kernel, fp32
+ * accumulation. K <= min(N, 256), N < 2^31, D a multiple of 16 in [16, 256], rows of U and items
+ * 16-byte aligned. The column range is cut into `splits` parts (<= 0: rs_fused_topk_splits; N /
+ * splits >= K) whose candidates go to ws (rs_fused_topk_ws_bytes; unused with one split) and
+ * are merged by rs_topk_rows inside the call. out_idx / out_val [B, ld_out]; out_val nullable.
+ * rs_rescore_rows: out_val[b, j] = fp32 dot of U[b] with items[cand[b, j]] (fp32 rows; the exact
+ * rescoring of bf16 candidates), for j < C; -inf where cand_val[b, j] (nullable) is -inf, so an
+ * excluded candidate stays excluded; a column outside [0, N) is not read and yields NaN. */
+int rs_fused_topk_splits(int B, int64_t N, int D, int K);                 /* host only: the automatic choice, >= 1 */
+int64_t rs_fused_topk_ws_bytes(int B, int64_t N, int D, int K, int splits);   /* host only; splits <= 0: automatic */
+int rs_fused_topk(const float* U, int64_t ldu, int B, const void* items, int items_bf16, int64_t ldi,
+                  int64_t N, int D, int K, const int64_t* user_ids, int64_t uid_stride,
+                  const int64_t* hist_off, const int32_t* hist_idx, int64_t num_users, int splits,
+                  void* ws, int64_t ws_bytes, int32_t* out_idx, float* out_val, int64_t ld_out,
+                  void* stream);
+int rs_rescore_rows(const float* U, int64_t ldu, int B, const float* items, int64_t ldi, int64_t N, int D,
+                    const int32_t* cand, const float* cand_val, int C, int64_t ld_cand, float* out_val,
+                    int64_t ld_out, void* stream);
 
 /* ---------------------------------------------------------------- clip + Adam
  * Flat multi-tensor path over a contiguous fp32 range (all parameters packed in one buffer).

@@ -556,3 +556,54 @@ def l2norm_bwd(y, norm, dy, eps=1e-12):
     dx = torch.empty_like(y)
     call('rs_l2norm_bwd', P(y), P(norm), P(dy), P(dx), M, N, float(eps), stream())
     return dx
+
+
+def fused_topk(U, items, K, user_ids=None, history=None, splits=0):
+    """The K best catalog columns of every user by dot product, and their scores, without the
+    [B, N] score matrix (rs_fused_topk). U [B, D] fp32; items [N, D] fp32 or bf16 (the dtype picks
+    the kernel); history = (off, idx, num_users) with each user's columns SORTED ascending
+    (retrieval.sorted_history_csr), applied when user_ids is given. -> (idx int32 [B, K],
+    val fp32 [B, K]), values descending, ties by the lower column. No CPU fallback."""
+    use_hist = history is not None and user_ids is not None
+    for t in (U, items) + ((user_ids,) + tuple(history[:2]) if use_hist else ()):
+        _hip.require_device(t)
+    if items.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'fused_topk: items must be float32 or bfloat16, got {items.dtype}')
+    U = U.float()
+    if U.stride(1) != 1 or U.stride(0) % 4 or U.data_ptr() % 16:
+        U = U.contiguous()
+    if items.stride(1) != 1 or (items.stride(0) * items.element_size()) % 16 or items.data_ptr() % 16:
+        items = items.contiguous()
+    B, D = int(U.shape[0]), int(U.shape[1])
+    N = int(items.shape[0])
+    L = _hip.lib()
+    if splits <= 0:
+        splits = L.rs_fused_topk_splits(B, N, D, K)
+    idx = torch.empty(B, K, device=U.device, dtype=torch.int32)
+    val = torch.empty(B, K, device=U.device, dtype=torch.float32)
+    nbytes = L.rs_fused_topk_ws_bytes(B, N, D, K, splits) if splits > 1 else 0
+    w = ws(nbytes, U.device) if splits > 1 else None
+    uid, us, off, hidx, nu = None, 0, None, None, 0
+    if use_hist:
+        uid = user_ids if user_ids.dtype == torch.int64 else user_ids.long()
+        us = int(uid.stride(0))
+        off, hidx, nu = history
+    call('rs_fused_topk', P(U), int(U.stride(0)), B, P(items), int(items.dtype == torch.bfloat16),
+         int(items.stride(0)), N, D, int(K), P(uid), us, P(off), P(hidx), int(nu), int(splits), P(w), int(nbytes),
+         P(idx), P(val), K, stream())
+    return idx, val
+
+
+def rescore_rows(U, items, cand, cand_val=None):
+    """out[b, j] = fp32 dot of U[b] with items[cand[b, j]] (rs_rescore_rows); -inf where cand_val is
+    -inf. U, items fp32 [., D]; cand int32 [B, C]."""
+    for t in (U, items, cand) + ((cand_val,) if cand_val is not None else ()):
+        _hip.require_device(t)
+    U, items, cand = U.contiguous(), items.contiguous(), cand.contiguous()
+    B, D = int(U.shape[0]), int(U.shape[1])
+    Cn = int(cand.shape[1])
+    cv = cand_val.contiguous() if cand_val is not None else None
+    out = torch.empty(B, Cn, device=U.device, dtype=torch.float32)
+    call('rs_rescore_rows', P(U), D, B, P(items), int(items.stride(0)), int(items.shape[0]), D, P(cand), P(cv),
+         Cn, Cn, P(out), Cn, stream())
+    return out

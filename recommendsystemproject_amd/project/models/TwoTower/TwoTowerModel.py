@@ -167,6 +167,21 @@ class TwoTowerModel(nn.Module):
     def get_item_embeddings(self, item_inputs):
         return self.item_tower(item_inputs, self.item_feature_mapping)
 
+    def recommend(self, user_inputs, index, k, user_ids=None, oversample=1):
+        """The k best items of `index` (retrieval.ItemIndex) for each user of `user_inputs` (a
+        user-tower batch): the user tower alone in eval mode under no_grad, then index.search.
+        -> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first."""
+        _hip.require_device(self.user_tower.feature_bn.weight)
+        ensure_flat(self)
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                user_emb = self.user_tower(user_inputs, self.user_feature_mapping)
+        finally:
+            self.train(was_training)
+        return index.search(user_emb, k, user_ids=user_ids, oversample=oversample)
+
     _NAN_MSG = {1: 'Found NaN in User Embedding', 2: 'Found NaN in Item Embedding',
                 4: 'Found NaN in Hard Negative Embedding'}
 

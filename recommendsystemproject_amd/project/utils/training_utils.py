@@ -197,11 +197,19 @@ def retrieval_topk(user_emb, all_item_embs, K, user_ids=None, history=None, chun
 
 def validate(model, loader, item_loader, device, epoch, k_list=[10, 20],
              item_id_feature='movie_id_enc', item_id_type='sparse', item_id_col_idx=0,
-             meta_data_loader=None, user_id_col_idx=None, log_embeddings=True, user_history=None):
+             meta_data_loader=None, user_id_col_idx=None, log_embeddings=True, user_history=None,
+             retrieval='staged'):
     """training_utils.py:121-275 on the device: item index through the item tower (eval mode),
     loss, MFMA scores U I_all^T, history mask, top-K and hit counts without host round trips
-    per user (the reference loops over users in Python); one sync at the end."""
+    per user (the reference loops over users in Python); one sync at the end.
+    retrieval='fused': the per-batch top-K through the fused kernel (ops.fused_topk on the fp32
+    embeddings, no score matrix) instead of retrieval_topk's staged pipeline; same lists. An
+    embedding width the kernel does not take (retrieval.fused_supported) stays on the staged path."""
     from recommendsystemproject_amd import _hip
+    if retrieval not in ('staged', 'fused'):
+        raise ValueError(f"retrieval must be 'staged' or 'fused', got {retrieval!r}")
+    from recommendsystemproject_amd import ops
+    from recommendsystemproject_amd.retrieval import fused_supported, sorted_history_csr
     model.eval()
     k_list = list(k_list)
     Kmax = max(k_list)
@@ -217,7 +225,10 @@ def validate(model, loader, item_loader, device, epoch, k_list=[10, 20],
         all_item_ids = torch.cat(ids_l, dim=0).view(-1).long()
     history = None
     if user_history is not None:
-        history = _history_csr(user_history, all_item_ids.cpu().numpy(), all_item_embs.device)
+        if retrieval == 'fused':
+            history = sorted_history_csr(user_history, all_item_ids.cpu().numpy(), all_item_embs.device)
+        else:
+            history = _history_csr(user_history, all_item_ids.cpu().numpy(), all_item_embs.device)
     if log_embeddings and epoch is not None:
         _log_embedding_stats(all_item_embs, epoch)
     meta_iter = iter(meta_data_loader) if meta_data_loader is not None else None
@@ -256,7 +267,10 @@ def validate(model, loader, item_loader, device, epoch, k_list=[10, 20],
                 else:
                     raise ValueError("Either metadata_loader or user_id_col_idx required")
                 user_ids = user_ids.long()
-            topk = retrieval_topk(user_emb, all_item_embs, Kmax, user_ids, history)
+            if retrieval == 'fused' and fused_supported(int(user_emb.shape[1])):
+                topk, _ = ops.fused_topk(user_emb, all_item_embs, Kmax, user_ids, history)
+            else:
+                topk = retrieval_topk(user_emb, all_item_embs, Kmax, user_ids, history)
             tg = targets.long()
             _hip.require_device(tg)
             _hip.call('rs_recall_hits', topk.data_ptr(), int(topk.shape[0]), Kmax, all_item_ids.data_ptr(),

@@ -1,0 +1,178 @@
+"""Serving: top-K items for users out of a trained two-tower model.
+
+ItemIndex holds the item tower's embeddings of a catalog (fp32, or bf16 rows at half the memory)
+and answers `search(user_emb, k)` with the fused retrieval kernel (csrc/retrieve.hip: scores are
+formed tile by tile on the MFMA and never stored). TwoTowerModel.recommend() runs the user tower
+and searches an index. The result is what validate()'s staged pipeline defines (values descending,
+ties by the lower catalog column, a user's history excluded).
+
+    index = ItemIndex.build(model, item_loader, device, dtype='bf16')
+    index.set_history(user_history)                       # optional: never recommend these again
+    item_ids, scores, cols = model.recommend(batch['user_tower'], index, k=20, user_ids=uids)
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import _hip, ops
+
+
+def fused_supported(D: int) -> bool:
+    """The embedding widths rs_fused_topk takes; others go through the staged retrieval_topk."""
+    return 16 <= D <= 256 and D % 16 == 0
+
+
+def sorted_history_csr(user_history, item_ids, device):
+    """user -> catalog column indices as device CSR (off [U+1] int64, idx int32, U), with
+    training_utils._history_csr's filters (ids <= the catalog's max id that are in the catalog) and
+    each user's columns sorted ascending and de-duplicated: what rs_fused_topk's binary search needs."""
+    ids = np.asarray(item_ids, dtype=np.int64).reshape(-1)
+    max_id = int(ids.max())
+    id_to_index = np.full(max_id + 1, -1, dtype=np.int64)
+    id_to_index[ids] = np.arange(len(ids))
+
+    def _uid(u):
+        try:
+            return int(u)
+        except (TypeError, ValueError):
+            return -1
+    users = [_uid(u) for u in user_history.keys() if _uid(u) >= 0]
+    U = (max(users) + 1) if users else 0
+    counts = np.zeros(U + 1, dtype=np.int64)
+    cols = []
+    for u in range(U):
+        items = user_history.get(u, user_history.get(np.int64(u), ()))
+        valid = [int(i) for i in items if 0 <= int(i) <= max_id]
+        c = id_to_index[valid] if valid else np.zeros(0, dtype=np.int64)
+        c = np.unique(c[c >= 0])  # sorted, distinct
+        counts[u + 1] = len(c)
+        cols.append(c)
+    off = np.cumsum(counts)
+    idx = np.concatenate(cols).astype(np.int32) if cols and off[-1] > 0 else np.zeros(1, dtype=np.int32)
+    return (torch.from_numpy(off).to(device), torch.from_numpy(idx).to(device), U)
+
+
+class ItemIndex:
+    """The item embeddings of a catalog, searchable by dot product. Column c of the index is row c
+    of the embeddings; `item_ids[c]` is its item id."""
+
+    def __init__(self, rows_fp32, rows_bf16, item_ids, dtype):
+        self._fp32 = rows_fp32
+        self._bf16 = rows_bf16
+        self.item_ids = item_ids
+        self._dtype = dtype
+        self._history = None
+
+    @classmethod
+    def from_embeddings(cls, embs, item_ids=None, dtype='fp32', keep_fp32=True):
+        if dtype not in ('fp32', 'bf16'):
+            raise ValueError(f"dtype must be 'fp32' or 'bf16', got {dtype!r}")
+        embs = embs.detach().float().contiguous()
+        if item_ids is None:
+            item_ids = torch.arange(embs.shape[0], device=embs.device, dtype=torch.int64)
+        item_ids = item_ids.detach().reshape(-1).long().to(embs.device)
+        if item_ids.numel() != embs.shape[0]:
+            raise ValueError(f'{item_ids.numel()} item ids for {embs.shape[0]} embeddings')
+        bf = embs.bfloat16() if dtype == 'bf16' else None
+        keep = dtype == 'fp32' or keep_fp32
+        return cls(embs if keep else None, bf, item_ids, dtype)
+
+    @classmethod
+    def build(cls, model, item_loader, device, dtype='fp32', item_id_feature='movie_id_enc',
+              item_id_type='sparse', item_id_col=0, keep_fp32=True):
+        """validate()'s indexing loop: the item tower in eval mode over the loader's batches."""
+        from .project.utils.training_utils import extract_item_id, to_device
+        was_training = model.training
+        model.eval()
+        embs, ids = [], []
+        try:
+            with torch.no_grad():
+                for item_batch in item_loader:
+                    item_batch = to_device(item_batch, device)
+                    embs.append(model.get_item_embeddings(item_batch))
+                    ids.append(extract_item_id(item_batch, feature_name=item_id_feature, feature_type=item_id_type,
+                                               item_id_col=item_id_col))
+        finally:
+            model.train(was_training)
+        return cls.from_embeddings(torch.cat(embs, dim=0), torch.cat(ids, dim=0).view(-1).long(), dtype=dtype,
+                                   keep_fp32=keep_fp32)
+
+    def __len__(self):
+        return int(self.item_ids.numel())
+
+    @property
+    def dim(self):
+        return int(self._rows().shape[1])
+
+    @property
+    def dtype(self):
+        return self._dtype
+
+    @property
+    def embeddings(self):
+        """The fp32 rows (None for a bf16 index built with keep_fp32=False)."""
+        return self._fp32
+
+    def _rows(self):
+        return self._bf16 if self._dtype == 'bf16' else self._fp32
+
+    def set_history(self, user_history):
+        """Exclude each user's items (user -> iterable of item ids, as build_user_history makes)
+        from that user's results; None clears it. search() then needs user_ids."""
+        self._history = None
+        if user_history is not None:
+            self._history = sorted_history_csr(user_history, self.item_ids.cpu().numpy(), self.item_ids.device)
+
+    def search(self, user_emb, k, user_ids=None, oversample=1):
+        """-> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first."""
+        rows = self._rows()
+        k = int(k)
+        if k < 1 or k > len(self):
+            raise ValueError(f'selected index k out of range (k={k}, items={len(self)})')
+        if oversample > 1 and self._fp32 is None:
+            raise ValueError('oversample > 1 rescores with the fp32 rows: build the index with keep_fp32=True')
+        _hip.require_device(user_emb)
+        _hip.require_device(rows)
+        hist = self._history if user_ids is not None else None
+        U = user_emb.detach().float().contiguous()
+        if not fused_supported(self.dim):
+            cols, val = self._search_staged(U, k, user_ids, hist)
+        elif oversample > 1 and self._dtype == 'bf16':
+            C = min(256, int(oversample) * k, len(self))
+            cand, cval = ops.fused_topk(U, rows, C, user_ids, hist)
+            exact = ops.rescore_rows(U, self._fp32, cand, cval)
+            cols = torch.empty(U.shape[0], k, device=U.device, dtype=torch.int32)
+            val = torch.empty(U.shape[0], k, device=U.device, dtype=torch.float32)
+            _hip.call('rs_topk_rows', exact.data_ptr(), C, int(U.shape[0]), C, k, cand.data_ptr(), C, 0,
+                      cols.data_ptr(), val.data_ptr(), k, ops.stream())
+        else:
+            cols, val = ops.fused_topk(U, rows, k, user_ids, hist)
+        return self.item_ids[cols.long()], val, cols
+
+    def _search_staged(self, U, k, user_ids, hist):
+        """Embedding widths the fused kernel does not take: the staged pipeline, scores gathered."""
+        from .project.utils.training_utils import retrieval_topk
+        rows = self._fp32 if self._fp32 is not None else self._bf16.float()
+        uid = user_ids.long() if user_ids is not None else None
+        cols = retrieval_topk(U, rows, k, uid, hist)
+        val = ops.rescore_rows(U, rows, cols)
+        if hist is not None:
+            val = self._mask_gathered(val, cols, uid.reshape(-1), hist, len(self))
+        return cols, val
+
+    @staticmethod
+    def _mask_gathered(val, cols, uid, hist, ncols):
+        """-inf at the gathered scores whose column is in the user's history slice: the CSR is
+        user-major and sorted within a user, so user * ncols + column is one sorted key array."""
+        off, idx, nu = hist
+        total = int(off[-1].item()) if nu else 0
+        if total == 0:
+            return val
+        owner = torch.repeat_interleave(torch.arange(nu, device=off.device), off[1:] - off[:-1])
+        keys = owner * ncols + idx[:total].long()
+        ok = (uid >= 0) & (uid < nu)
+        q = uid.clamp(0, nu - 1).view(-1, 1) * ncols + cols.long()
+        pos = torch.searchsorted(keys, q.contiguous()).clamp(max=total - 1)
+        hit = (keys[pos] == q) & ok.view(-1, 1)
+        return val.masked_fill(hit, float('-inf'))
