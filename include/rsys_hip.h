@@ -219,7 +219,8 @@ int rs_ffn_bwd_ln_bf16(int M, int F, const float* x, const float* W1, const floa
 /* rs_ffn_bwd_ln_bf16 with norm2's backward as its prologue (bf16 mode, F = 256, M % 16 == 0):
  * x2 = LN2(x1 + drop2(ffn(x1))) with x1 = LN1(h1). Reads dy2 = dL/dx2 and h2 (+ norm2's
  * mean2 / rstd2 / gamma2) instead of dff / dres; writes dff = drop2(dh2) [M, 64] (the operand of
- * rs_ffn_wgrad_bf16), dh1, dsa (p > 0) and accumulates dgamma1/dbeta1, dgamma2/dbeta2
+ * rs_ffn_wgrad_bf16), dh1, dsa (p > 0; NULL: not stored, for rs_outproj_bwd_bf16, which masks dh1
+ * itself) and accumulates dgamma1/dbeta1, dgamma2/dbeta2
  * (fixed-order partials in ws: rs_ffn_bwd_ln2_ws_bytes). Replaces rs_layernorm_bwd (norm2) +
  * rs_ffn_bwd_ln_bf16 of TransformerEncoderLayer's backward (SequenceEncoder.py:17-29; post-LN,
  * norm_first=False). Only dh1 may alias dy2. */
@@ -255,6 +256,19 @@ int rs_wgrad_bf16(int rows, int Mo, int No, const void* dy, int ldy, int dy_bf16
  * Replaces rs_wgrad_bf16 + the input-gradient GEMM of nn.MultiheadAttention's in_proj
  * (SequenceEncoder.py:17-29), which streamed dqkv twice. Deterministic; the reduction defers under
  * rs_reduce_defer. ws: rs_linear_bwd_bf16_ws_bytes (0: shape not covered). */
+/* The attention out-projection's whole backward from ONE read of dh = dh1 [M, 64] (norm1's
+ * backward; only read), bf16 mode: y = dh * mask(key, site) (rs_dropout_fwd's draw of element
+ * m * 64 + c; p == 0: y = dh), dW[64][64] += y^T x, db += colsum(y) (fp32, before rounding),
+ * dx[M][64] = y W (fp32). x = the attention output [M, 64] and dh contiguous fp32, W [64][ldw], dW
+ * contiguous. Replaces the dsa store of rs_ffn_bwd_ln2_bf16, rs_wgrad_bf16 and the input-gradient
+ * GEMM of nn.MultiheadAttention's out_proj (SequenceEncoder.py:17-29) with their bits (row split,
+ * MFMA order and reduce of the former, k map of the latter's bf16 streaming instance).
+ * Deterministic; the reduction defers under rs_reduce_defer. ws: rs_outproj_bwd_bf16_ws_bytes
+ * (0: shape not covered). */
+int64_t rs_outproj_bwd_bf16_ws_bytes(int M, int d);
+int rs_outproj_bwd_bf16(const float* dh, const float* x, const float* W, int ldw, int M, int d, float p,
+                        const int64_t* key, int site, float* dx, float* dW, float* db, float* ws,
+                        void* stream);
 int64_t rs_linear_bwd_bf16_ws_bytes(int M, int N, int K);
 int rs_linear_bwd_bf16(const void* dy, const float* x, const float* W, int ldw, int M, int N, int K,
                        const float* dx_in, float* dx, float* dW, float* db, float* ws, void* stream);

@@ -73,6 +73,8 @@ SIGNATURES = {
     'rs_wgrad_bf16': (i32, [i32, i32, i32, vp, i32, i32, vp, i32, i32, f32, vp, i32, vp, vp, vp]),
     'rs_linear_bwd_bf16_ws_bytes': (i64, [i32, i32, i32]),
     'rs_linear_bwd_bf16': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    'rs_outproj_bwd_bf16_ws_bytes': (i64, [i32, i32]),
+    'rs_outproj_bwd_bf16': (i32, [vp, vp, vp, i32, i32, i32, f32, vp, i32, vp, vp, vp, vp, vp]),
     'rs_colsum_ws_bytes': (i64, [i32, i32]),
     'rs_colsum': (i32, [vp, i32, i32, i32, f32, f32, vp, vp, vp]),
     'rs_gather_fwd': (i32, [vp, i32, i32, vp, i32, vp, vp]),

@@ -258,7 +258,9 @@ __global__ __launch_bounds__(512) void ffn_fwd_bf16_kernel(FfnArgs a) {
 // 16t + 4q + e (the layout of the residual add after the last product), so dh2 IS the residual
 // gradient; dff = drop2(dh2) is stored (fp32, for rs_ffn_wgrad_bf16) and goes through a per-wave
 // LDS tile as bf16 to reach the 16q .. 16q+15 layout of the dff W2 product's operand.
-template <int F, bool LN1 = false, bool LNDROP = false, bool ACTS = true, bool LN2 = false>
+// DA (with LNDROP): dsa = drop1(dh1) is stored to ln_da; without it only dh1 is written (the
+// one-pass out-projection backward, linear_bwd.hip, applies the mask to dh1 itself).
+template <int F, bool LN1 = false, bool LNDROP = false, bool ACTS = true, bool LN2 = false, bool DA = true>
 __global__ __launch_bounds__(512) void ffn_bwd_bf16_kernel(FfnArgs a) {
   static_assert(!LN2 || (LN1 && !ACTS), "LN2 prologue needs the LN1 epilogue and no activations");
   constexpr int FP = F + 8;
@@ -331,7 +333,7 @@ __global__ __launch_bounds__(512) void ffn_bwd_bf16_kernel(FfnArgs a) {
       lpg[t] = floatx4{0.f, 0.f, 0.f, 0.f};
       lpb[t] = floatx4{0.f, 0.f, 0.f, 0.f};
     }
-    if constexpr (LNDROP) ldk = make_key(a.key, a.ln_site, a.p);
+    if constexpr (LNDROP && DA) ldk = make_key(a.key, a.ln_site, a.p);
   }
   for (; g < groups; g += stride) {
     int zo = 0;
@@ -500,7 +502,7 @@ __global__ __launch_bounds__(512) void ffn_bwd_bf16_kernel(FfnArgs a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) dh[e] = lrs * (gg[t][e] - s1 - xh[t][e] * s2);
         *reinterpret_cast<floatx4*>(a.dx + m * D + 16 * t + 4 * q) = dh;
-        if constexpr (LNDROP) {
+        if constexpr (LNDROP && DA) {
           float mk[4];
           keep4(ldk, (uint64_t)(m * D + 16 * t + 4 * q), mk);  // rs_dropout_fwd's draw
 #pragma unroll
@@ -901,7 +903,8 @@ extern "C" int rs_ffn_bwd_ln2_bf16(int M, int F, const float* x, const float* W1
                    aligned16(b1) && aligned16(h1) && aligned16(gamma1) && aligned16(gamma2) &&
                    (!dsa || aligned16(dsa)),
                "rs_ffn_bwd_ln2_bf16: misaligned operand");
-  RS_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || (key && dsa)), "rs_ffn_bwd_ln2_bf16: dropout needs a key and dsa, 0 <= p < 1");
+  // dsa null with p > 0: dsa is not stored (the caller masks dh1 itself: rs_outproj_bwd_bf16)
+  RS_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || key), "rs_ffn_bwd_ln2_bf16: dropout needs a key, 0 <= p < 1");
   if (M == 0) return 0;
   FfnArgs a{};
   a.M = M; a.x = x; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.mask = const_cast<uint64_t*>(mask);
@@ -914,7 +917,8 @@ extern "C" int rs_ffn_bwd_ln2_bf16(int M, int F, const float* x, const float* W1
   a.ln2_ws = ws + (int64_t)nb * 128;
   const size_t lds = bwd_ln2_lds(F);
   hipStream_t st = as_stream(stream);
-  if (p > 0.f) ffn_bwd_bf16_kernel<256, true, true, false, true><<<nb, 512, lds, st>>>(a);
+  if (p > 0.f && dsa) ffn_bwd_bf16_kernel<256, true, true, false, true><<<nb, 512, lds, st>>>(a);
+  else if (p > 0.f) ffn_bwd_bf16_kernel<256, true, true, false, true, false><<<nb, 512, lds, st>>>(a);
   else ffn_bwd_bf16_kernel<256, true, false, false, true><<<nb, 512, lds, st>>>(a);
   RS_CHECK_LAUNCH("rs_ffn_bwd_ln2_bf16");
   // both LayerNorms' gamma / beta partials in one reduce launch (same order of operations per job)

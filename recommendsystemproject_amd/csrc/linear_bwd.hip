@@ -10,6 +10,8 @@
 // Every output carries the bits of the kernels it replaces: the row split is wgrad_bf16_launch's
 // (the same chunks meet the same MFMAs in the same order, the same number of partials meets the
 // same reduce), and dcat uses rowgemm_bf16_kernel's k map and MFMA order.
+// The same kernel with ONE mask is the attention out-projection's backward (rs_outproj_bwd_bf16):
+// dx = dh1, cat = att, W = Wo; y = dh1 * mask is the dsa the FFN backward no longer stores.
 //
 // Structure: wgrad_bf16_kernel's (gemm_stream.hip). A workgroup of 4 waves owns a row range; rows
 // are staged 32 at a time through registers into row-major bf16 LDS images of y and cat (double
@@ -45,8 +47,8 @@ struct SeqBwdArgs {
   int site_a, site_b;
 };
 
-// NCP: dcat padded to a multiple of 32
-template <int NCP>
+// NCP: dcat padded to a multiple of 32. ONE: a single mask (site_a; the out-projection's dropout1).
+template <int NCP, bool ONE = false>
 __global__ __launch_bounds__(256) void seq_input_bwd_bf16_kernel(SeqBwdArgs a, int rows_per_block) {
   constexpr int PY = wb_pitch(SB_D), PX = wb_pitch(NCP);
   constexpr int TMT = SB_D / 32, TNT = NCP / 32;
@@ -68,7 +70,7 @@ __global__ __launch_bounds__(256) void seq_input_bwd_bf16_kernel(SeqBwdArgs a, i
   DropKey ka{}, kb{};
   if (drop) {
     ka = make_key(a.key, a.site_a, a.p);
-    kb = make_key(a.key, a.site_b, a.p);
+    if constexpr (!ONE) kb = make_key(a.key, a.site_b, a.p);
   }
   typedef const __attribute__((address_space(1))) floatx4* gptr4;
 
@@ -128,11 +130,13 @@ __global__ __launch_bounds__(256) void seq_input_bwd_bf16_kernel(SeqBwdArgs a, i
       float ma[4] = {1.f, 1.f, 1.f, 1.f};
       if (drop) {
         const uint64_t e0 = (uint64_t)m * SB_D + c;
-        float mb[4];
-        keep4(kb, e0, mb);
-        keep4(ka, e0, ma);
+        if constexpr (!ONE) {
+          float mb[4];
+          keep4(kb, e0, mb);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] *= mb[e];
+          for (int e = 0; e < 4; ++e) v[e] *= mb[e];
+        }
+        keep4(ka, e0, ma);
       }
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
@@ -552,6 +556,36 @@ extern "C" int rs_seq_input_bwd_bf16(const float* dx, const float* cat, int ldca
   const int begins[2] = {0, d * dcat};
   const float one[2] = {1.f, 1.f};
   return reduce_job(ws, nblk, d * dcat + d, 2, outs, begins, one, one, st);
+}
+
+// The attention out-projection's backward on the same kernel: dh = dh1 (norm1's backward, only
+// read), x = att, W = Wo [64][ldw]; y = dh * keep4(site) is the dsa that ffn_bwd_bf16_kernel used to
+// store for wgrad_bf16_kernel<64, 64> and the input-gradient rowgemm, whose bits these outputs carry.
+extern "C" int64_t rs_outproj_bwd_bf16_ws_bytes(int M, int d) { return rs_seq_input_bwd_bf16_ws_bytes(M, d, SB_D); }
+
+extern "C" int rs_outproj_bwd_bf16(const float* dh, const float* x, const float* W, int ldw, int M, int d,
+                                   float p, const int64_t* key, int site, float* dx, float* dW, float* db,
+                                   float* ws, void* stream) {
+  RS_CHECK_ARG(M >= 0 && d == SB_D, "rs_outproj_bwd_bf16: need d == 64 (d=%d)", d);
+  if (M == 0) return 0;
+  RS_CHECK_ARG(dh && x && W && dx && dW && db && ws, "rs_outproj_bwd_bf16: null operand");
+  RS_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || key), "rs_outproj_bwd_bf16: 0 <= p < 1, key with p > 0");
+  RS_CHECK_ARG(aligned16(dh) && aligned16(x) && aligned16(dx) && aligned16(ws) && ldw >= d,
+               "rs_outproj_bwd_bf16: misaligned operand");
+  RS_CHECK_ARG(dx != dh && dx != x, "rs_outproj_bwd_bf16: dx may not alias an input");
+  SeqBwdArgs a{};
+  a.dx = dh; a.cat = x; a.W = W; a.dcat = dx; a.ws = ws;
+  a.M = M; a.NC = SB_D; a.ldcat = SB_D; a.ldw = ldw;
+  a.p = p; a.key = key; a.site_a = site; a.site_b = site;
+  const int rpb = seq_bwd_rows(M), nblk = cdiv(M, rpb);
+  const size_t lds = seq_bwd_lds(SB_D);
+  hipStream_t st = as_stream(stream);
+  seq_input_bwd_bf16_kernel<SB_D, true><<<nblk, 256, lds, st>>>(a, rpb);
+  RS_CHECK_LAUNCH("rs_outproj_bwd_bf16");
+  float* outs[2] = {dW, db};
+  const int begins[2] = {0, SB_D * SB_D};
+  const float one[2] = {1.f, 1.f};
+  return reduce_job(ws, nblk, SB_D * SB_D + SB_D, 2, outs, begins, one, one, st);
 }
 
 extern "C" int64_t rs_linear_bwd_bf16_ws_bytes(int M, int N, int K) {

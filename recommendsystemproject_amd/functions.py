@@ -454,6 +454,11 @@ def _post_attn_bwd(lyr, saved, dx2, p, key, site):
     x, qkv, att, lse, h1, x1, m1, r1, f1, h2, m2, r2 = saved
     g = grad_of
     sa_mod = lyr.self_attn
+    Wo, gWo = sa_mod.out_proj.weight, g(sa_mod.out_proj.weight)
+    # bf16 mode, token-sized layer: dsa = drop1(dh1) is never stored; the out-projection's weight,
+    # bias and input gradients come from one read of dh1 (csrc/linear_bwd.hip). dh1 is a fresh
+    # allocation of dx2's shape and layout, so the check runs on dx2
+    fuse = isinstance(f1, tuple) and ops.outproj_bwd_fused_ok(dx2, att, Wo, gWo)
     # x2 = LN2(x1 + drop2(ff))
     ln1_done = False
     if isinstance(f1, tuple):
@@ -463,7 +468,7 @@ def _post_attn_bwd(lyr, saved, dx2, p, key, site):
         dh1, dsa, dff = ops.ffn_bwd_ln2_bf16(
             x1, lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, f1[1], dx2, h2, lyr.norm2.weight,
             m2, r2, g(lyr.norm2.weight), g(lyr.norm2.bias), h1, lyr.norm1.weight, m1, r1,
-            g(lyr.norm1.weight), g(lyr.norm1.bias), p, key, site + 1, site + 3)
+            g(lyr.norm1.weight), g(lyr.norm1.bias), p, key, site + 1, site + 3, dsa=not fuse)
         ln1_done = True
         ops.ffn_wgrad_bf16(x1, lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, f1[1], dff, p,
                            g(lyr.linear1.weight), g(lyr.linear1.bias), g(lyr.linear2.weight),
@@ -484,10 +489,12 @@ def _post_attn_bwd(lyr, saved, dx2, p, key, site):
         dsa = torch.empty_like(dh2) if p > 0 else None
         dh1 = ops.layernorm_bwd(h1, dh2, lyr.norm1.weight, m1, r1, g(lyr.norm1.weight), g(lyr.norm1.bias),
                                 da=dsa, p=p, key=key, site=site + 1)
+    if fuse:
+        return dh1, ops.outproj_bwd_fused(dh1, att, Wo, p, key, site + 1, gWo, g(sa_mod.out_proj.bias))
     if dsa is None:  # p == 0: dsa IS dh1 (read here before the in-proj backward accumulates into it)
         dsa = dh1
-    ops.linear_bwd_weight(dsa, att, g(sa_mod.out_proj.weight), db=g(sa_mod.out_proj.bias))
-    datt = ops.linear_bwd_input(dsa, sa_mod.out_proj.weight)
+    ops.linear_bwd_weight(dsa, att, gWo, db=g(sa_mod.out_proj.bias))
+    datt = ops.linear_bwd_input(dsa, Wo)
     return dh1, datt
 
 

@@ -182,13 +182,14 @@ def ffn_bwd_ln_bf16(x, W1, b1, W2, mask, dff, dres, h1, gamma1, mean1, rstd1, dg
 
 
 def ffn_bwd_ln2_bf16(x, W1, b1, W2, mask, dy2, h2, gamma2, mean2, rstd2, dgamma2, dbeta2, h1, gamma1,
-                     mean1, rstd1, dgamma1, dbeta1, p, key, site1, site2):
+                     mean1, rstd1, dgamma1, dbeta1, p, key, site1, site2, dsa=True):
     """norm2's backward + the FFN backward + norm1's backward in one pass (weight gradients by
-    ffn_wgrad_bf16 from the returned dff): -> (dh1, dsa or None, dff = drop2(dh2))."""
+    ffn_wgrad_bf16 from the returned dff): -> (dh1, dsa or None, dff = drop2(dh2)). dsa=False:
+    dsa = drop1(dh1) is not stored (None; outproj_bwd_fused masks dh1 itself)."""
     M, F = x.shape[0], W1.shape[0]
     dff = torch.empty_like(dy2)
     dh1 = torch.empty_like(dy2)
-    dsa = torch.empty_like(dy2) if p > 0 else None
+    dsa = torch.empty_like(dy2) if p > 0 and dsa else None
     w = ws(_hip.lib().rs_ffn_bwd_ln2_ws_bytes(M, F), x.device)
     call('rs_ffn_bwd_ln2_bf16', M, F, P(x), P(W1), P(b1), P(W2), P(mask), P(dy2), P(h2), P(gamma2), P(mean2),
          P(rstd2), P(dff), P(dgamma2), P(dbeta2), P(h1), P(gamma1), P(mean1), P(rstd1), P(dh1), P(dsa),
@@ -248,6 +249,33 @@ def linear_bwd_fused(dy, x, W, dW, db, dx_in=None):
     call('rs_linear_bwd_bf16', P(dy), P(x), P(W), W.stride(0), M, N, K, P(dx_in), P(dx), P(dW), P(db), P(w),
          stream())
     return dx
+
+
+def outproj_bwd_fused_ok(dh, att, W, dW):
+    """The one-pass backward of the attention out-projection (csrc/linear_bwd.hip
+    rs_outproj_bwd_bf16): bf16 compute mode, d_model 64, RSYS_OUTPROJ_BWD_FUSED not 0, and a token
+    count at which the pair it replaces is the bf16 streaming pair (wgrad_bf16 and the bf16 row GEMM:
+    >= 32,768 rows, a multiple of 16), whose bits it reproduces. Below that the input gradient is an
+    fp32-MFMA GEMM (the pruned last layer's B rows), which stays as it is."""
+    if precision.compute_dtype() != 'bf16' or os.environ.get('RSYS_OUTPROJ_BWD_FUSED', '1') == '0':
+        return False
+    M, d = dh.shape
+    return (d == 64 and M >= STREAM_BF16_MIN_ROWS and M % 16 == 0 and
+            dh.dtype == torch.float32 and att.dtype == torch.float32 and dh.is_contiguous() and
+            att.is_contiguous() and tuple(att.shape) == (M, d) and tuple(W.shape) == (d, d) and
+            W.stride(1) == 1 and dW.is_contiguous() and _aligned16(dh, att) and
+            _hip.lib().rs_outproj_bwd_bf16_ws_bytes(M, d) > 0)
+
+
+def outproj_bwd_fused(dh, att, W, p, key, site, dW, db):
+    """dW += y^T att, db += colsum(y), returns datt = y W with y = dh * mask(key, site) (p == 0:
+    y = dh), from one read of dh, which is not written (rs_outproj_bwd_bf16)."""
+    M, d = dh.shape
+    datt = torch.empty(M, d, device=dh.device, dtype=torch.float32)
+    w = ws(_hip.lib().rs_outproj_bwd_bf16_ws_bytes(M, d), dh.device)
+    call('rs_outproj_bwd_bf16', P(dh), P(att), P(W), W.stride(0), M, d, float(p), P(key) if p > 0 else None, site,
+         P(datt), P(dW), P(db), P(w), stream())
+    return datt
 
 
 def colsum(X, out, *, scale=1.0, beta=1.0, M=None, N=None, ldx=None):

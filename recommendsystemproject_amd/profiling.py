@@ -176,7 +176,7 @@ def _ffn_bwd_ln2_work(a):
     M, F = a[0], a[1]
     # dy2, h2, h1 read, dff, dh1 (+ dsa) written (fp32); mask bits; both rows' mean / rstd
     return (4.0 * M * F * 64 + 24.0 * M * 64,
-            4.0 * M * 64 * (5 + (1 if a[23] > 0 else 0)) + 16.0 * M + M * F / 8.0)
+            4.0 * M * 64 * (5 + (1 if a[23] > 0 and a[20] else 0)) + 16.0 * M + M * F / 8.0)
 
 
 WORK = {
@@ -197,6 +197,8 @@ WORK = {
                                      a[4] * (2.0 * a[5] + 4.0 * a[6] * (3 if a[7] else 2))),
     # one pass: dx read, cat read, dcat written; dW = y^T cat and dcat = y W
     'rs_seq_input_bwd_bf16': lambda a: (4.0 * a[5] * a[6] * a[7], 4.0 * a[5] * (a[6] + 2 * a[7])),
+    # the out-projection's one pass: dh and att read, datt written; dW = y^T att and datt = y W
+    'rs_outproj_bwd_bf16': lambda a: (4.0 * a[4] * a[5] * a[5], 12.0 * a[4] * a[5]),
     # its companion's second read of dx [rows, N] (one fma per element; the partials are small)
     'rs_seq_input_pos_grad': lambda a: (2.0 * a[1] * a[2], 4.0 * a[1] * a[2]),
     'rs_inbatch_ce_fwd': _ce_work,
