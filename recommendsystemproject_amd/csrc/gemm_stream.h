@@ -47,7 +47,16 @@ int wgrad_launch(const StreamArgs& s, hipStream_t st);
 // bf16 MFMA weight gradient; y_bf16 / x_bf16: dY (A) / X (B) are stored as bf16
 int wgrad_bf16_launch(const StreamArgs& s, bool y_bf16, bool x_bf16, hipStream_t st);
 
-// bf16 weight-gradient geometry (wgrad_bf16_kernel, and linear_bwd.hip's fused backward)
+// The row split of every weight-gradient kernel (fp32, bf16, and linear_bwd.hip's one-pass
+// backwards): workgroups of rows_per_block rows, whole chunks of bk rows each; `blocks` partial
+// tiles meet the fixed-order reduce. A fused backward has the bits of the pair it replaces only
+// while both use this split, and the *_ws_bytes sizes follow it. max_blocks bounds `blocks` for
+// any chunk height (rs_wgrad_ws_bytes sizes for either kernel).
+struct RowSplit { int rows_per_block, blocks, max_blocks; };
+RowSplit wgrad_row_split(int rows, int bk);
+
+// bf16 weight-gradient geometry (wgrad_tile.h: the tile of wgrad_bf16_kernel and of the one-pass
+// backwards)
 constexpr int WB_BK = 32;  // rows per staged chunk
 
 // LDS row pitch (bf16 elements) for a pad-wide image: the 4 rows of one transposed read must
@@ -63,6 +72,11 @@ constexpr int wb_gm(int tm, int tn) {
     if (c < cost) { cost = c; best = gm; }
   }
   return best;
+}
+
+// bytes of the double-buffered bf16 staging images of Y [WB_BK][mo_pad] and X [WB_BK][no_pad]
+constexpr size_t wb_stage_bytes(int mo_pad, int no_pad) {
+  return (size_t)2 * WB_BK * (wb_pitch(mo_pad) + wb_pitch(no_pad)) * 2;
 }
 
 }  // namespace rs

@@ -26,6 +26,7 @@
 #include "rng.h"
 #include "mfma.h"
 #include "stage.h"
+#include "wgrad_tile.h"
 
 namespace rs {
 
@@ -585,16 +586,15 @@ __global__ __launch_bounds__(1024) void wgrad_reduce_kernel(StreamArgs a, int P)
 // delivers from the row-major image (two transposed reads per fragment). The bias gradient
 // colsum(dY) is taken from the fp32 registers before rounding (per-thread partials, then a
 // fixed-order sum over the chunk's rows): it is exact fp32 as in the fp32 kernel.
-// WB_BK, wb_pitch, wb_gm: gemm_stream.h (shared with linear_bwd.hip)
+// Everything behind the LDS images (wave grid, transposed reads, MFMA order, partial-tile write,
+// ordered column sum) is WgradTile's (wgrad_tile.h), shared with linear_bwd.hip.
 
 // YB / XB: the operand is stored as bf16 in HBM (16-byte loads carry 8 elements and go to LDS
 // as they are); otherwise fp32 (4 elements per load, rounded to bf16 on the way to LDS)
 template <int MO_PAD, int NO_PAD, bool YB, bool XB>
 __global__ __launch_bounds__(256) void wgrad_bf16_kernel(StreamArgs a, int rows_per_block) {
-  constexpr int PY = wb_pitch(MO_PAD), PX = wb_pitch(NO_PAD);
-  constexpr int TMT = MO_PAD / 32, TNT = NO_PAD / 32;
-  constexpr int GM = wb_gm(TMT, TNT), GN = 4 / GM;
-  constexpr int TM = (TMT + GM - 1) / GM, TN = (TNT + GN - 1) / GN;
+  typedef WgradTile<MO_PAD, NO_PAD> Tile;
+  constexpr int PY = Tile::PY, PX = Tile::PX;
   constexpr int VY = YB ? 8 : 4, VX = XB ? 8 : 4;  // elements per 16-byte slot
   constexpr int ysl = WB_BK * MO_PAD / VY, xsl = WB_BK * NO_PAD / VX;
   constexpr int MAXS = (ysl + xsl + 255) / 256;
@@ -602,11 +602,10 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(StreamArgs a, int rows_
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __bf16* Ys = reinterpret_cast<__bf16*>(smem_raw);  // [2][WB_BK][PY]
   __bf16* Xs = Ys + 2 * WB_BK * PY;                    // [2][WB_BK][PX]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const int Mo = a.M, No = a.N;
   const int r0 = blockIdx.x * rows_per_block;
   const int r1 = min(a.K, r0 + rows_per_block);
-  const int wm = wave / GN, wn = wave % GN;
   const unsigned char* Ag = reinterpret_cast<const unsigned char*>(a.A);
   const unsigned char* Bg = reinterpret_cast<const unsigned char*>(a.B);
   constexpr int EY = YB ? 2 : 4, EX = XB ? 2 : 4;  // bytes per element in HBM
@@ -665,18 +664,7 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(StreamArgs a, int rows_
       }
     }
   };
-  floatx16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  // transposed-read addresses: lane 4q+p of 16-lane group g reads row q (+4 for the second
-  // half of the fragment) of the block, columns 4p..4p+3 of the 16-column half (g & 1);
-  // rows 8h.. with h = g >> 1
-  const int g = lane >> 4, lq = (lane & 15) >> 2, lp = lane & 3;
-  const int trow = 8 * (g >> 1) + lq, tcol = 16 * (g & 1) + 4 * lp;
+  Tile tile(tid);
 
   int buf = 0;
   if (r0 < r1) {
@@ -687,80 +675,17 @@ __global__ __launch_bounds__(256) void wgrad_bf16_kernel(StreamArgs a, int rows_
   for (int c0 = r0; c0 < r1; c0 += WB_BK) {
     const bool more = c0 + WB_BK < r1;
     if (more) load_chunk(c0 + WB_BK);
-    const __bf16* Y = Ys + buf * WB_BK * PY;
-    const __bf16* X = Xs + buf * WB_BK * PX;
-#pragma unroll
-    for (int ks = 0; ks < WB_BK / 16; ++ks) {
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int ti = wm * TM + i;
-        const __bf16* p = Y + (16 * ks + trow) * PY + 32 * (ti < TMT ? ti : 0) + tcol;
-        af[i] = tr_frag(p, p + 4 * PY);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int tj = wn * TN + j;
-        const __bf16* p = X + (16 * ks + trow) * PX + 32 * (tj < TNT ? tj : 0) + tcol;
-        bfr[j] = tr_frag(p, p + 4 * PX);
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
+    tile.product(Ys + buf * WB_BK * PY, Xs + buf * WB_BK * PX);
     if (more) store_chunk(buf ^ 1);
     __syncthreads();
     buf ^= 1;
   }
   // partial tile -> ws[block][Mo][No] (fixed-order reduce later)
-  float* out = a.ws + (int64_t)blockIdx.x * Mo * No;
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int ti = wm * TM + i;
-    if (ti >= TMT) continue;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int tj = wn * TN + j;
-      if (tj >= TNT) continue;
-      const int n = tj * 32 + (lane & 31);
-      if (n >= No) continue;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = ti * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        if (m < Mo) out[(int64_t)m * No + n] = acc[i][j][e];
-      }
-    }
+  tile.write(a.ws + (int64_t)blockIdx.x * Mo * No, Mo, No);
+  if (a.rowsum != nullptr) {  // column partials through the staging LDS
+    const float rsum = Tile::column_sum(reinterpret_cast<float*>(smem_raw), ysum, tid, Mo);
+    if (tid < Mo) a.ws[(int64_t)gridDim.x * Mo * No + (int64_t)blockIdx.x * Mo + tid] = rsum;
   }
-  if (a.rowsum != nullptr) {
-    // per-thread column partials -> R[kk][c] (reusing the staging LDS), then rows summed in order
-    float* R = reinterpret_cast<float*>(smem_raw);
-#pragma unroll
-    for (int i = 0; i < NYS; ++i) {
-      const int s = tid + i * 256;
-      if (s < ysl)
-#pragma unroll
-        for (int e = 0; e < VY; ++e) R[s * VY + e] = ysum[i][e];
-    }
-    __syncthreads();
-    if (tid < Mo) {
-      float rsum = 0.f;
-#pragma unroll 8
-      for (int kk = 0; kk < WB_BK; ++kk) rsum += R[kk * MO_PAD + tid];
-      a.ws[(int64_t)gridDim.x * Mo * No + (int64_t)blockIdx.x * Mo + tid] = rsum;
-    }
-  }
-}
-
-int wgrad_blocks(int Kr) {
-  // row splits: 512 measured best at C2 (256 -> 0.101, 384 -> 0.091, 512 -> 0.083, 768 -> 0.082,
-  // 1024 -> 0.099 ms per step of rs_wgrad_bf16; DESIGN.md §3)
-  constexpr int cap = 512;
-  int nb = Kr / 64;  // >= 64 rows per workgroup; short K (the MLP's B = 4096) still fills 64 CUs
-  if (nb > cap) nb = cap;
-  if (nb < 1) nb = 1;
-  return nb;
 }
 
 
@@ -1108,15 +1033,33 @@ int rowgemm_ln_launch(const StreamArgs& s, hipStream_t st) {
   return 0;
 }
 
+// The (mo_pad, no_pad) dW tiles with an instance of wgrad_kernel and of wgrad_bf16_kernel (fp32
+// operands): written once, the dispatches below are generated from it.
+#define RS_WGRAD_INSTANCES(X)                                                                       \
+  X(64, 64) X(64, 256) X(256, 64) X(192, 64) X(64, 192) X(128, 128) X(128, 64) X(64, 128) X(32, 64) \
+  X(64, 32) X(128, 256) X(256, 128) X(64, 96) X(96, 64)                                             \
+  X(256, 192)  // the user tower's first Linear (172 inputs): generic split-K GEMM + reduce was 32 us
+
 bool wgrad_instance(int M, int N) {
   const int mo_pad = (M + 31) / 32 * 32, no_pad = (N + 31) / 32 * 32;
+#define RS_WI(MOV, NOV) case MOV * 1000 + NOV:
   switch (mo_pad * 1000 + no_pad) {
-    case 64064: case 64256: case 256064: case 192064: case 64192: case 128128: case 128064:
-    case 64128: case 32064: case 64032: case 128256: case 256128: case 64096: case 96064:
-    case 256192:  // the user tower's first Linear (172 inputs): generic split-K GEMM + reduce was 32 us
+    RS_WGRAD_INSTANCES(RS_WI)
       return true;
     default: return false;
   }
+#undef RS_WI
+}
+
+RowSplit wgrad_row_split(int rows, int bk) {
+  // row splits: 512 measured best at C2 (256 -> 0.101, 384 -> 0.091, 512 -> 0.083, 768 -> 0.082,
+  // 1024 -> 0.099 ms per step of rs_wgrad_bf16; DESIGN.md §3)
+  constexpr int cap = 512;
+  int nb = rows / 64;  // >= 64 rows per workgroup; short K (the MLP's B = 4096) still fills 64 CUs
+  if (nb > cap) nb = cap;
+  if (nb < 1) nb = 1;
+  const int rpb = cdiv(cdiv(rows, nb), bk) * bk;
+  return {rpb, cdiv(rows, rpb), nb};
 }
 
 bool wgrad_supported(int transA, int transB, int M, int N, int K, const float* A, int lda,
@@ -1130,7 +1073,7 @@ bool wgrad_supported(int transA, int transB, int M, int N, int K, const float* A
 }
 
 int64_t wgrad_ws_bytes(int M, int N, int K) {
-  return (int64_t)wgrad_blocks(K) * ((int64_t)M * N + M) * (int64_t)sizeof(float);
+  return (int64_t)wgrad_row_split(K, WG_BK).max_blocks * ((int64_t)M * N + M) * (int64_t)sizeof(float);
 }
 
 // wgrad_reduce_kernel's work as deferred jobs (reduce.hip) while the library defers reductions:
@@ -1151,10 +1094,9 @@ bool wgrad_reduce_deferred(const StreamArgs& s, int P) {
 
 int wgrad_bf16_launch(const StreamArgs& s, bool y_bf16, bool x_bf16, hipStream_t st) {
   const int mo_pad = (s.M + 31) / 32 * 32, no_pad = (s.N + 31) / 32 * 32;
-  const int nb = wgrad_blocks(s.K);
-  const int rpb = cdiv(cdiv(s.K, nb), WB_BK) * WB_BK;
-  const int nblk = cdiv(s.K, rpb);
-  const size_t stage = (size_t)2 * WB_BK * (wb_pitch(mo_pad) + wb_pitch(no_pad)) * 2;
+  const RowSplit sp = wgrad_row_split(s.K, WB_BK);
+  const int rpb = sp.rows_per_block, nblk = sp.blocks;
+  const size_t stage = wb_stage_bytes(mo_pad, no_pad);
   const size_t red = (size_t)WB_BK * mo_pad * sizeof(float);
   const size_t lds = stage > red ? stage : red;
   const int key = (mo_pad * 1000 + no_pad) * 4 + (y_bf16 ? 2 : 0) + (x_bf16 ? 1 : 0);
@@ -1162,12 +1104,9 @@ int wgrad_bf16_launch(const StreamArgs& s, bool y_bf16, bool x_bf16, hipStream_t
   case (MOV * 1000 + NOV) * 4 + (YB ? 2 : 0) + (XB ? 1 : 0):                       \
     wgrad_bf16_kernel<MOV, NOV, YB, XB><<<nblk, 256, lds, st>>>(s, rpb);           \
     break;
+#define RS_WBF(MOV, NOV) RS_WB(MOV, NOV, false, false)
   switch (key) {
-    RS_WB(64, 64, false, false) RS_WB(64, 256, false, false) RS_WB(256, 64, false, false)
-    RS_WB(192, 64, false, false) RS_WB(64, 192, false, false) RS_WB(128, 128, false, false)
-    RS_WB(128, 64, false, false) RS_WB(64, 128, false, false) RS_WB(32, 64, false, false)
-    RS_WB(64, 32, false, false) RS_WB(128, 256, false, false) RS_WB(256, 128, false, false)
-    RS_WB(64, 96, false, false) RS_WB(96, 64, false, false) RS_WB(256, 192, false, false)
+    RS_WGRAD_INSTANCES(RS_WBF)
     RS_WB(64, 256, false, true) RS_WB(256, 64, true, false)  // the fused FFN's weight gradients
     RS_WB(192, 64, true, false)  // in_proj from the bf16 dqkv (RS_ATTN_QKV_BF16)
     default:
@@ -1175,6 +1114,7 @@ int wgrad_bf16_launch(const StreamArgs& s, bool y_bf16, bool x_bf16, hipStream_t
                 (int)x_bf16);
       return -1;
   }
+#undef RS_WBF
 #undef RS_WB
   RS_CHECK_LAUNCH("wgrad bf16");
   if (wgrad_reduce_deferred(s, nblk)) return 0;
@@ -1186,19 +1126,16 @@ int wgrad_bf16_launch(const StreamArgs& s, bool y_bf16, bool x_bf16, hipStream_t
 
 int wgrad_launch(const StreamArgs& s, hipStream_t st) {
   const int mo_pad = (s.M + 31) / 32 * 32, no_pad = (s.N + 31) / 32 * 32;
-  const int nb = wgrad_blocks(s.K);
-  const int rpb = cdiv(cdiv(s.K, nb), WG_BK) * WG_BK;
-  const int nblk = cdiv(s.K, rpb);
   if (s.epi & RS_GEMM_BF16) return wgrad_bf16_launch(s, false, false, st);
+  const RowSplit sp = wgrad_row_split(s.K, WG_BK);
+  const int rpb = sp.rows_per_block, nblk = sp.blocks;
   const size_t lds = (size_t)2 * WG_BK * (mo_pad + no_pad) * sizeof(float);
 #define RS_WG(MOV, NOV)                                                   \
   case MOV * 1000 + NOV:                                                  \
     wgrad_kernel<MOV, NOV><<<nblk, 256, lds, st>>>(s, rpb);               \
     break;
   switch (mo_pad * 1000 + no_pad) {
-    RS_WG(64, 64) RS_WG(64, 256) RS_WG(256, 64) RS_WG(192, 64) RS_WG(64, 192) RS_WG(128, 128)
-    RS_WG(128, 64) RS_WG(64, 128) RS_WG(32, 64) RS_WG(64, 32) RS_WG(128, 256) RS_WG(256, 128)
-    RS_WG(64, 96) RS_WG(96, 64) RS_WG(256, 192)
+    RS_WGRAD_INSTANCES(RS_WG)
     default: set_error("wgrad: no instance for %dx%d", s.M, s.N); return -1;
   }
 #undef RS_WG

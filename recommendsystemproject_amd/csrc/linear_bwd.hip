@@ -13,19 +13,24 @@
 // The same kernel with ONE mask is the attention out-projection's backward (rs_outproj_bwd_bf16):
 // dx = dh1, cat = att, W = Wo; y = dh1 * mask is the dsa the FFN backward no longer stores.
 //
-// Structure: wgrad_bf16_kernel's (gemm_stream.hip). A workgroup of 4 waves owns a row range; rows
-// are staged 32 at a time through registers into row-major bf16 LDS images of y and cat (double
-// buffered, two further chunks in flight in registers: one chunk per 4-wave workgroup does not
-// cover the HBM latency). The masks are applied to the fp32 registers on the way (keep4 of element
-// row * 64 + col: the draws of rs_dropout_*). dW reads both images transposed
-// (ds_read_b64_tr_b16, 32x32x16 MFMA); dcat reads the y image as it lies (rows = MFMA columns,
-// 16x16x32 MFMA with W on the row side, so a lane holds 4 consecutive output columns) against W
-// fragments kept in registers for the whole kernel. Each workgroup writes one partial row
-// [dW | db]; one fixed-order reduce job with two output ranges adds them to the gradients.
+// Shared pieces: the weight-gradient side of both kernels here (wave grid, transposed reads, MFMA
+// order, partial-tile write, ordered column sum) is WgradTile (wgrad_tile.h), the one
+// wgrad_bf16_kernel uses; the row split is wgrad_row_split (gemm_stream.h), the one
+// wgrad_bf16_launch uses; the pipeline of both kernels is stream_two_sets below; the launch tail
+// is reduce_partials. A kernel here adds its own loads, masks, input-gradient product and stores.
+// A workgroup of 4 waves owns a row range; rows are staged 32 at a time through registers into
+// row-major bf16 LDS images of y and cat (double buffered, two further chunks in flight in
+// registers: one chunk per 4-wave workgroup does not cover the HBM latency). The masks are applied
+// to the fp32 registers on the way (keep4 of element row * 64 + col: the draws of rs_dropout_*).
+// dcat reads the y image as it lies (rows = MFMA columns, 16x16x32 MFMA with W on the row side, so
+// a lane holds 4 consecutive output columns) against W fragments kept in registers for the whole
+// kernel. Each workgroup writes one partial row [dW | db]; one fixed-order reduce job with two
+// output ranges adds them to the gradients.
 #include "common.h"
 #include "gemm_stream.h"
 #include "mfma.h"
 #include "rng.h"
+#include "wgrad_tile.h"
 
 #include <type_traits>
 
@@ -34,6 +39,34 @@ namespace rs {
 namespace {
 
 constexpr int SB_D = 64;  // encoder width (dx columns)
+
+// The pipeline of a workgroup's row range [r0, r1): chunk j lives in LDS buffer j & 1 and travels
+// through register set j & 1, two chunks in flight in registers behind the one in LDS.
+//   load_chunk(SET, c0)        requests the chunk at row c0 into register set SET
+//   store_chunk(SET, buf, c0)  consumes set SET into LDS buffer buf (past the range: zeros)
+//   step(NXT, buf, c0)         computes on buffer buf; then store_chunk(NXT, buf ^ 1, c0 + WB_BK):
+//     the next chunk, requested two steps ago, whose loads are consumed BEFORE this chunk's global
+//     stores are issued (stores and loads share vmcnt); then those stores; then
+//     load_chunk(NXT, c0 + 3 * WB_BK) behind them, and a barrier
+// Whole pairs in the loop, an odd last chunk after it: an exit between the two steps would give
+// the wait counts a path on which the older register set looks like the newer one (vmcnt(0)).
+typedef std::integral_constant<int, 0> set0;
+typedef std::integral_constant<int, 1> set1;
+template <class Load, class Store, class Step>
+__device__ __forceinline__ void stream_two_sets(int r0, int r1, Load&& load_chunk, Store&& store_chunk,
+                                                Step&& step) {
+  load_chunk(set0{}, r0);
+  store_chunk(set0{}, 0, r0);
+  load_chunk(set1{}, r0 + WB_BK);
+  load_chunk(set0{}, r0 + 2 * WB_BK);
+  __syncthreads();
+  int c0 = r0;
+  for (; c0 + WB_BK < r1; c0 += 2 * WB_BK) {
+    step(set1{}, 0, c0);
+    step(set0{}, 1, c0 + WB_BK);
+  }
+  if (c0 < r1) step(set1{}, 0, c0);
+}
 
 struct SeqBwdArgs {
   const float* dx;   // [M][64]
@@ -50,10 +83,8 @@ struct SeqBwdArgs {
 // NCP: dcat padded to a multiple of 32. ONE: a single mask (site_a; the out-projection's dropout1).
 template <int NCP, bool ONE = false>
 __global__ __launch_bounds__(256) void seq_input_bwd_bf16_kernel(SeqBwdArgs a, int rows_per_block) {
-  constexpr int PY = wb_pitch(SB_D), PX = wb_pitch(NCP);
-  constexpr int TMT = SB_D / 32, TNT = NCP / 32;
-  constexpr int GM = wb_gm(TMT, TNT), GN = 4 / GM;
-  constexpr int TM = (TMT + GM - 1) / GM, TN = (TNT + GN - 1) / GN;
+  typedef WgradTile<SB_D, NCP> Tile;
+  constexpr int PY = Tile::PY, PX = Tile::PX;
   constexpr int NYS = WB_BK * SB_D / 4 / 256;  // dx float4 slots per thread (2)
   constexpr int NXS = WB_BK * NCP / 4 / 256;   // cat float4 slots per thread
   constexpr int NTW = NCP / 32;                // dcat column tiles (16 wide) per wave
@@ -65,7 +96,6 @@ __global__ __launch_bounds__(256) void seq_input_bwd_bf16_kernel(SeqBwdArgs a, i
   const int NC = a.NC;
   const int r0 = blockIdx.x * rows_per_block;
   const int r1 = min(a.M, r0 + rows_per_block);
-  const int wm = wave / GN, wn = wave % GN;
   const bool drop = a.p > 0.f;
   DropKey ka{}, kb{};
   if (drop) {
@@ -152,49 +182,10 @@ __global__ __launch_bounds__(256) void seq_input_bwd_bf16_kernel(SeqBwdArgs a, i
       put4(&Xs[(buf * WB_BK + kk) * PX + c], c0 + kk < r1 && c < NC ? sx[S][i] : floatx4{0.f, 0.f, 0.f, 0.f});
     }
   };
-  floatx16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  // transposed-read addresses (wgrad_bf16_kernel)
-  const int g = lane >> 4, lq = (lane & 15) >> 2, lp = lane & 3;
-  const int trow = 8 * (g >> 1) + lq, tcol = 16 * (g & 1) + 4 * lp;
-
-  typedef std::integral_constant<int, 0> set0;
-  typedef std::integral_constant<int, 1> set1;
-  load_chunk(set0{}, r0);
-  store_chunk(set0{}, 0, r0);
-  load_chunk(set1{}, r0 + WB_BK);
-  load_chunk(set0{}, r0 + 2 * WB_BK);
-  __syncthreads();
-  // chunk j of the range lives in LDS buffer j & 1 and travels through register set j & 1
+  Tile tile(tid);
   auto step = [&](auto NXT, int buf, int c0) {
     const __bf16* Y = Ys + buf * WB_BK * PY;
-    const __bf16* X = Xs + buf * WB_BK * PX;
-#pragma unroll
-    for (int ks = 0; ks < WB_BK / 16; ++ks) {
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int ti = wm * TM + i;
-        const __bf16* p = Y + (16 * ks + trow) * PY + 32 * (ti < TMT ? ti : 0) + tcol;
-        af[i] = tr_frag(p, p + 4 * PY);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int tj = wn * TN + j;
-        const __bf16* p = X + (16 * ks + trow) * PX + 32 * (tj < TNT ? tj : 0) + tcol;
-        bfr[j] = tr_frag(p, p + 4 * PX);
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
+    tile.product(Y, Xs + buf * WB_BK * PX);
     // dcat rows 16*rg .. +15 of the chunk, this wave's column tiles
     floatx4 dacc[NTW];
     {
@@ -209,10 +200,7 @@ __global__ __launch_bounds__(256) void seq_input_bwd_bf16_kernel(SeqBwdArgs a, i
           dacc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[t][u], yf[u], dacc[t], 0, 0, 0);
       }
     }
-    // the next chunk (requested two iterations ago) goes to the other buffer; its loads are
-    // consumed here, BEFORE this chunk's dcat stores are issued (stores and loads share vmcnt),
-    // and its registers then request the chunk three ahead, behind the stores
-    store_chunk(NXT, buf ^ 1, c0 + WB_BK);  // (past the range: zeros)
+    store_chunk(NXT, buf ^ 1, c0 + WB_BK);  // before this chunk's dcat stores (stream_two_sets)
     {
       const int m = c0 + 16 * rg + r;
 #pragma unroll
@@ -224,62 +212,24 @@ __global__ __launch_bounds__(256) void seq_input_bwd_bf16_kernel(SeqBwdArgs a, i
     load_chunk(NXT, c0 + 3 * WB_BK);
     __syncthreads();
   };
-  // whole pairs in the loop, an odd last chunk after it: an exit between the two steps would give
-  // the wait counts a path on which the older register set looks like the newer one (vmcnt(0))
-  int c0 = r0;
-  for (; c0 + WB_BK < r1; c0 += 2 * WB_BK) {
-    step(set1{}, 0, c0);
-    step(set0{}, 1, c0 + WB_BK);
-  }
-  if (c0 < r1) step(set1{}, 0, c0);
-  // partial row of this workgroup: [dW 64 x NC | db 64]
+  stream_two_sets(r0, r1, load_chunk, store_chunk, step);
+  // partial row of this workgroup: [dW 64 x NC | db 64]; the column partials go through the
+  // staging LDS
   float* out = a.ws + (int64_t)blockIdx.x * (SB_D * NC + SB_D);
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int ti = wm * TM + i;
-    if (ti >= TMT) continue;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int tj = wn * TN + j;
-      if (tj >= TNT) continue;
-      const int n = tj * 32 + (lane & 31);
-      if (n >= NC) continue;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = ti * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        out[(int64_t)m * NC + n] = acc[i][j][e];
-      }
-    }
-  }
-  // per-thread column partials -> R[kk][c] (reusing the staging LDS), then rows summed in order
-  float* R = reinterpret_cast<float*>(smem_raw);
-#pragma unroll
-  for (int i = 0; i < NYS; ++i)
-    *reinterpret_cast<floatx4*>(R + (tid + i * 256) * 4) = floatx4{ysum[i][0], ysum[i][1], ysum[i][2], ysum[i][3]};
-  __syncthreads();
-  if (tid < SB_D) {
-    float rsum = 0.f;
-#pragma unroll 8
-    for (int kk = 0; kk < WB_BK; ++kk) rsum += R[kk * SB_D + tid];
-    out[SB_D * NC + tid] = rsum;
-  }
+  tile.write(out, SB_D, NC);
+  const float rsum = Tile::column_sum(reinterpret_cast<float*>(smem_raw), ysum, tid, SB_D);
+  if (tid < SB_D) out[SB_D * NC + tid] = rsum;
 }
 
 int seq_bwd_pad(int NC) { return (NC + 31) / 32 * 32; }
 
-size_t seq_bwd_lds(int NC) {
-  const int ncp = seq_bwd_pad(NC);
-  return (size_t)2 * WB_BK * (wb_pitch(SB_D) + wb_pitch(ncp)) * 2;
-}
-
-// rows per workgroup: wgrad_bf16_launch's split (up to 512 workgroups of >= 64 rows, whole chunks
-// each; C2: 416 rows, 493 workgroups), so that the partial sums -- and with them the gradients'
-// bits -- are those of the weight-gradient kernel these replace
-int seq_bwd_rows(int M) {
-  int nb = M / 64;
-  if (nb > 512) nb = 512;
-  if (nb < 1) nb = 1;
-  return cdiv(cdiv(M, nb), WB_BK) * WB_BK;
+// The launch tail of every entry point here: dW += the sum of the nblk partial rows' [Mo x No]
+// parts, db += that of their [Mo] parts, in one fixed-order reduce job with two output ranges.
+int reduce_partials(const float* ws, int nblk, int Mo, int No, float* dW, float* db, hipStream_t st) {
+  float* outs[2] = {dW, db};
+  const int begins[2] = {0, Mo * No};
+  const float one[2] = {1.f, 1.f};
+  return reduce_job(ws, nblk, Mo * No + Mo, 2, outs, begins, one, one, st);
 }
 
 bool seq_bwd_shape_ok(int M, int d, int NC) {
@@ -309,10 +259,8 @@ struct LinBwdArgs {
 
 template <bool RES>
 __global__ __launch_bounds__(256) void linear_bwd_bf16_kernel(LinBwdArgs a, int rows_per_block) {
-  constexpr int PY = wb_pitch(LB_N), PX = wb_pitch(LB_K), PW = LB_N + 8;
-  constexpr int TMT = LB_N / 32, TNT = LB_K / 32;
-  constexpr int GM = wb_gm(TMT, TNT), GN = 4 / GM;
-  constexpr int TM = (TMT + GM - 1) / GM, TN = (TNT + GN - 1) / GN;
+  typedef WgradTile<LB_N, LB_K> Tile;
+  constexpr int PY = Tile::PY, PX = Tile::PX, PW = LB_N + 8;
   constexpr int NYS = WB_BK * LB_N / 8 / 256;  // dY 16-byte slots (8 bf16) per thread (3)
   constexpr int NXS = WB_BK * LB_K / 4 / 256;  // X float4 slots per thread (2)
   constexpr int KC = LB_N / 64;                // 64-wide k chunks of the dx product
@@ -324,7 +272,6 @@ __global__ __launch_bounds__(256) void linear_bwd_bf16_kernel(LinBwdArgs a, int 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r0 = blockIdx.x * rows_per_block;
   const int r1 = min(a.M, r0 + rows_per_block);
-  const int wm = wave / GN, wn = wave % GN;
   const int r = lane & 15, q = lane >> 4;
   const int rg = wave & 1;  // 16-row group of the chunk; column tiles (wave >> 1) and (wave >> 1) + 2
   typedef const __attribute__((address_space(1))) floatx4* gptr4;
@@ -397,47 +344,10 @@ __global__ __launch_bounds__(256) void linear_bwd_bf16_kernel(LinBwdArgs a, int 
       for (int t = 0; t < 2; ++t) res[t] = sr[S][t];
     }
   };
-  floatx16 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
-  const int g = lane >> 4, lq = (lane & 15) >> 2, lp = lane & 3;
-  const int trow = 8 * (g >> 1) + lq, tcol = 16 * (g & 1) + 4 * lp;
-
-  typedef std::integral_constant<int, 0> set0;
-  typedef std::integral_constant<int, 1> set1;
-  load_chunk(set0{}, r0);
-  store_chunk(set0{}, 0, r0);
-  load_chunk(set1{}, r0 + WB_BK);
-  load_chunk(set0{}, r0 + 2 * WB_BK);
-  __syncthreads();
+  Tile tile(tid);
   auto step = [&](auto NXT, int buf, int c0) {
     const __bf16* Y = Ys + buf * WB_BK * PY;
-    const __bf16* X = Xs + buf * WB_BK * PX;
-#pragma unroll
-    for (int ks = 0; ks < WB_BK / 16; ++ks) {
-      bf16x8 af[TM], bfr[TN];
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        const int ti = wm * TM + i;
-        const __bf16* p = Y + (16 * ks + trow) * PY + 32 * (ti < TMT ? ti : 0) + tcol;
-        af[i] = tr_frag(p, p + 4 * PY);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int tj = wn * TN + j;
-        const __bf16* p = X + (16 * ks + trow) * PX + 32 * (tj < TNT ? tj : 0) + tcol;
-        bfr[j] = tr_frag(p, p + 4 * PX);
-      }
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[i], bfr[j], acc[i][j], 0, 0, 0);
-    }
+    tile.product(Y, Xs + buf * WB_BK * PX);
     // dx rows 16*rg .. +15 of the chunk, two column tiles per wave, K = 192
     floatx4 dacc[2];
 #pragma unroll
@@ -457,8 +367,7 @@ __global__ __launch_bounds__(256) void linear_bwd_bf16_kernel(LinBwdArgs a, int 
 #pragma unroll
       for (int t = 0; t < 2; ++t) dacc[t] += res[t];
     }
-    // (as above) the next chunk's loads are consumed before this chunk's stores are issued
-    store_chunk(NXT, buf ^ 1, c0 + WB_BK);
+    store_chunk(NXT, buf ^ 1, c0 + WB_BK);  // before this chunk's dx stores (stream_two_sets)
     {
       const int m = c0 + 16 * rg + r;
 #pragma unroll
@@ -468,49 +377,19 @@ __global__ __launch_bounds__(256) void linear_bwd_bf16_kernel(LinBwdArgs a, int 
     load_chunk(NXT, c0 + 3 * WB_BK);
     __syncthreads();
   };
-  int c0 = r0;
-  for (; c0 + WB_BK < r1; c0 += 2 * WB_BK) {
-    step(set1{}, 0, c0);
-    step(set0{}, 1, c0 + WB_BK);
-  }
-  if (c0 < r1) step(set1{}, 0, c0);
-  // partial row of this workgroup: [dW 192 x 64 | db 192]
+  stream_two_sets(r0, r1, load_chunk, store_chunk, step);
+  // partial row of this workgroup: [dW 192 x 64 | db 192]; the column partials go over the dY images
   float* out = a.ws + (int64_t)blockIdx.x * (LB_N * LB_K + LB_N);
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int ti = wm * TM + i;
-    if (ti >= TMT) continue;
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int tj = wn * TN + j;
-      if (tj >= TNT) continue;
-      const int n = tj * 32 + (lane & 31);
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int m = ti * 32 + (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5);
-        out[(int64_t)m * LB_K + n] = acc[i][j][e];
-      }
-    }
-  }
-  float* R = reinterpret_cast<float*>(smem_raw);  // [WB_BK][192] over the dY images
-#pragma unroll
-  for (int i = 0; i < NYS; ++i)
-#pragma unroll
-    for (int e = 0; e < 8; ++e) R[(tid + i * 256) * 8 + e] = ysum[i][e];
-  __syncthreads();
-  if (tid < LB_N) {
-    float rsum = 0.f;
-#pragma unroll 8
-    for (int kk = 0; kk < WB_BK; ++kk) rsum += R[kk * LB_N + tid];
-    out[LB_N * LB_K + tid] = rsum;
-  }
+  tile.write(out, LB_N, LB_K);
+  const float rsum = Tile::column_sum(reinterpret_cast<float*>(smem_raw), ysum, tid, LB_N);
+  if (tid < LB_N) out[LB_N * LB_K + tid] = rsum;
 }
 
 // 65 KB of dynamic LDS (40 KB of staging, 25 KB of W): above the 64 KB of the CDNA parts before
 // gfx950, within its 160 KB (two workgroups per CU); the library is built for gfx950 only, and
 // RS_CHECK_LAUNCH reports a launch that any other target would refuse
 size_t lin_bwd_lds() {
-  return (size_t)(2 * WB_BK * (wb_pitch(LB_N) + wb_pitch(LB_K)) + LB_K * (LB_N + 8)) * 2;
+  return wb_stage_bytes(LB_N, LB_K) + (size_t)LB_K * (LB_N + 8) * 2;
 }
 
 }  // namespace
@@ -524,7 +403,7 @@ extern "C" int rs_seq_input_bwd_bf16_supported(int M, int d, int dcat) {
 
 extern "C" int64_t rs_seq_input_bwd_bf16_ws_bytes(int M, int d, int dcat) {
   if (!seq_bwd_shape_ok(M, d, dcat)) return 0;
-  return (int64_t)cdiv(M, seq_bwd_rows(M)) * ((int64_t)d * dcat + d) * (int64_t)sizeof(float);
+  return (int64_t)wgrad_row_split(M, WB_BK).blocks * ((int64_t)d * dcat + d) * (int64_t)sizeof(float);
 }
 
 extern "C" int rs_seq_input_bwd_bf16(const float* dx, const float* cat, int ldcat, const float* W, int ldw,
@@ -543,8 +422,9 @@ extern "C" int rs_seq_input_bwd_bf16(const float* dx, const float* cat, int ldca
   a.dx = dx; a.cat = cat; a.W = W; a.dcat = dcat_out; a.ws = ws;
   a.M = M; a.NC = dcat; a.ldcat = ldcat; a.ldw = ldw;
   a.p = p; a.key = key; a.site_a = site_a; a.site_b = site_b;
-  const int rpb = seq_bwd_rows(M), nblk = cdiv(M, rpb);
-  const size_t lds = seq_bwd_lds(dcat);
+  const RowSplit sp = wgrad_row_split(M, WB_BK);
+  const int rpb = sp.rows_per_block, nblk = sp.blocks;
+  const size_t lds = wb_stage_bytes(SB_D, seq_bwd_pad(dcat));
   hipStream_t st = as_stream(stream);
   switch (seq_bwd_pad(dcat)) {
     case 32: seq_input_bwd_bf16_kernel<32><<<nblk, 256, lds, st>>>(a, rpb); break;
@@ -552,10 +432,7 @@ extern "C" int rs_seq_input_bwd_bf16(const float* dx, const float* cat, int ldca
     default: seq_input_bwd_bf16_kernel<96><<<nblk, 256, lds, st>>>(a, rpb); break;
   }
   RS_CHECK_LAUNCH("rs_seq_input_bwd_bf16");
-  float* outs[2] = {dW, db};
-  const int begins[2] = {0, d * dcat};
-  const float one[2] = {1.f, 1.f};
-  return reduce_job(ws, nblk, d * dcat + d, 2, outs, begins, one, one, st);
+  return reduce_partials(ws, nblk, d, dcat, dW, db, st);
 }
 
 // The attention out-projection's backward on the same kernel: dh = dh1 (norm1's backward, only
@@ -577,20 +454,17 @@ extern "C" int rs_outproj_bwd_bf16(const float* dh, const float* x, const float*
   a.dx = dh; a.cat = x; a.W = W; a.dcat = dx; a.ws = ws;
   a.M = M; a.NC = SB_D; a.ldcat = SB_D; a.ldw = ldw;
   a.p = p; a.key = key; a.site_a = site; a.site_b = site;
-  const int rpb = seq_bwd_rows(M), nblk = cdiv(M, rpb);
-  const size_t lds = seq_bwd_lds(SB_D);
+  const RowSplit sp = wgrad_row_split(M, WB_BK);
+  const int rpb = sp.rows_per_block, nblk = sp.blocks;
   hipStream_t st = as_stream(stream);
-  seq_input_bwd_bf16_kernel<SB_D, true><<<nblk, 256, lds, st>>>(a, rpb);
+  seq_input_bwd_bf16_kernel<SB_D, true><<<nblk, 256, wb_stage_bytes(SB_D, SB_D), st>>>(a, rpb);
   RS_CHECK_LAUNCH("rs_outproj_bwd_bf16");
-  float* outs[2] = {dW, db};
-  const int begins[2] = {0, SB_D * SB_D};
-  const float one[2] = {1.f, 1.f};
-  return reduce_job(ws, nblk, SB_D * SB_D + SB_D, 2, outs, begins, one, one, st);
+  return reduce_partials(ws, nblk, SB_D, SB_D, dW, db, st);
 }
 
 extern "C" int64_t rs_linear_bwd_bf16_ws_bytes(int M, int N, int K) {
   if (M < 1 || N != LB_N || K != LB_K) return 0;
-  return (int64_t)cdiv(M, seq_bwd_rows(M)) * (LB_N * LB_K + LB_N) * (int64_t)sizeof(float);
+  return (int64_t)wgrad_row_split(M, WB_BK).blocks * (LB_N * LB_K + LB_N) * (int64_t)sizeof(float);
 }
 
 extern "C" int rs_linear_bwd_bf16(const void* dy, const float* x, const float* W, int ldw, int M, int N, int K,
@@ -605,13 +479,11 @@ extern "C" int rs_linear_bwd_bf16(const void* dy, const float* x, const float* W
   LinBwdArgs a{};
   a.dy = reinterpret_cast<const __bf16*>(dy); a.x = x; a.W = W; a.dx_in = dx_in; a.dx = dx; a.ws = ws;
   a.M = M; a.ldw = ldw;
-  const int rpb = seq_bwd_rows(M), nblk = cdiv(M, rpb);
+  const RowSplit sp = wgrad_row_split(M, WB_BK);
+  const int rpb = sp.rows_per_block, nblk = sp.blocks;
   hipStream_t st = as_stream(stream);
   if (dx_in) linear_bwd_bf16_kernel<true><<<nblk, 256, lin_bwd_lds(), st>>>(a, rpb);
   else linear_bwd_bf16_kernel<false><<<nblk, 256, lin_bwd_lds(), st>>>(a, rpb);
   RS_CHECK_LAUNCH("rs_linear_bwd_bf16");
-  float* outs[2] = {dW, db};
-  const int begins[2] = {0, LB_N * LB_K};
-  const float one[2] = {1.f, 1.f};
-  return reduce_job(ws, nblk, LB_N * LB_K + LB_N, 2, outs, begins, one, one, st);
+  return reduce_partials(ws, nblk, LB_N, LB_K, dW, db, st);
 }

@@ -299,3 +299,98 @@ def test_misaligned_views_take_the_unfused_path(bf16_mode, monkeypatch):
     assert not ops.linear_bwd_fused_ok(shifted(dy), x, W, dW)
     assert not ops.linear_bwd_fused_ok(dy, shifted(x), W, dW)
     assert not ops.linear_bwd_fused_ok(dy, x, W, dW, shifted(rnd(M, K, seed=25)))
+
+
+# ------------------------------------------------------------------------------------------
+# Exact check of the shared weight-gradient tile and row split, independent of both sides of the
+# fused-vs-unfused comparisons above (which now run the same tile code). Every operand is a small
+# integer: dy / dx, x / cat, W and the starting dW, db, dx_in lie in [-4, 4], the masks of p = 0.5
+# in {0, 2}. All of them are exact in bf16, and with at most 70,000 rows the largest sum is
+# 4 * 4 * 4 * 70,000 = 4.48M < 2^24, so every partial and final sum is exact in fp32 whatever the
+# order: the float64 torch reference, cast to fp32, must be met bit for bit.
+EXACT_ROWS = [
+    20,     # one ragged chunk
+    48,     # one workgroup: a whole chunk and a ragged one
+    64,     # two whole chunks: the paired loop with no tail
+    150,    # two workgroups
+    2050,   # 22 workgroups of three chunks: pair plus odd tail, ragged last workgroup
+    70000,  # 438 workgroups of five chunks
+]
+EXACT_KEY = (4321, 7)
+
+
+def ints(*shape, seed):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(-4, 5, shape, generator=g).float().to(DEV)
+
+
+def mask(M, d, p, site):
+    """The keep mask (scaled by 1 / (1 - p)) of rs_dropout_* at `site`; ones for p == 0."""
+    ones = torch.ones(M, d, device=DEV)
+    if p == 0:
+        return ones
+    key = torch.tensor(EXACT_KEY, dtype=torch.int64, device=DEV)
+    m = ops.dropout_bwd(ones, p, key, site)
+    assert p == 0.5 and bool(((m == 0) | (m == 2)).all())
+    return m
+
+
+def exact(got, ref64):
+    torch.cuda.synchronize()
+    ref = ref64.float()
+    assert ref.abs().max().item() < 2 ** 24
+    assert torch.equal(got, ref), (got - ref).abs().max().item()
+
+
+@pytest.mark.parametrize('M', EXACT_ROWS)
+@pytest.mark.parametrize('Mo,No,dy_bf16', [(64, 64, False), (64, 40, False), (192, 64, True)])
+def test_wgrad_bf16_exact_on_integers(Mo, No, dy_bf16, M):
+    dy, x = ints(M, Mo, seed=31), ints(M, No, seed=32)
+    dW0, db0 = ints(Mo, No, seed=33), ints(Mo, seed=34)
+    dW, db = dW0.clone(), db0.clone()
+    ops.wgrad_bf16(dy.to(torch.bfloat16) if dy_bf16 else dy, x, dW, db=db)
+    exact(dW, dW0.double() + dy.double().t() @ x.double())
+    exact(db, db0.double() + dy.double().sum(0))
+
+
+@pytest.mark.parametrize('M', EXACT_ROWS)
+@pytest.mark.parametrize('dcat', [24, 40, 72])
+def test_seq_input_bwd_fused_exact_on_integers(dcat, M):
+    d, L, p = 64, 2, 0.5
+    dx, cat, W = ints(M, d, seed=41), ints(M, dcat, seed=42), ints(d, dcat, seed=43)
+    dW0, db0 = ints(d, dcat, seed=44), ints(d, seed=45)
+    y = (dx * mask(M, d, p, 1) * mask(M, d, p, 0)).double()
+    dW, db, pos = dW0.clone(), db0.clone(), torch.zeros(L, d, device=DEV)
+    key = torch.tensor(EXACT_KEY, dtype=torch.int64, device=DEV)
+    out = ops.seq_input_bwd_fused(dx, cat, W, L, p, key, 0, 1, dW, db, pos)
+    exact(out, y @ W.double())
+    exact(dW, dW0.double() + y.t() @ cat.double())
+    exact(db, db0.double() + y.sum(0))
+
+
+@pytest.mark.parametrize('M', EXACT_ROWS)
+@pytest.mark.parametrize('p', [0.0, 0.5])
+def test_outproj_bwd_fused_exact_on_integers(p, M):
+    d, site = 64, 3
+    dh, att, W = ints(M, d, seed=51), ints(M, d, seed=52), ints(d, d, seed=53)
+    dW0, db0 = ints(d, d, seed=54), ints(d, seed=55)
+    y = (dh * mask(M, d, p, site)).double()
+    dW, db = dW0.clone(), db0.clone()
+    key = torch.tensor(EXACT_KEY, dtype=torch.int64, device=DEV)
+    datt = ops.outproj_bwd_fused(dh, att, W, p, key, site, dW, db)
+    exact(datt, y @ W.double())
+    exact(dW, dW0.double() + y.t() @ att.double())
+    exact(db, db0.double() + y.sum(0))
+
+
+@pytest.mark.parametrize('M', EXACT_ROWS)
+@pytest.mark.parametrize('res', [False, True])
+def test_linear_bwd_fused_exact_on_integers(res, M):
+    N, K = 192, 64
+    dy, x, W = ints(M, N, seed=61), ints(M, K, seed=62), ints(N, K, seed=63)
+    dW0, db0, dx0 = ints(N, K, seed=64), ints(N, seed=65), ints(M, K, seed=66)
+    dW, db = dW0.clone(), db0.clone()
+    dx = ops.linear_bwd_fused(dy.to(torch.bfloat16), x, W, dW, db, dx_in=dx0.clone() if res else None)
+    exact(dx, dy.double() @ W.double() + (dx0.double() if res else 0))
+    exact(dW, dW0.double() + dy.double().t() @ x.double())
+    exact(db, db0.double() + dy.double().sum(0))

@@ -14,6 +14,27 @@ def test_ws_bytes_follow_the_weight_gradient_split():
     assert L.rs_outproj_bwd_bf16_ws_bytes(204800, 32) == 0  # not covered
 
 
+@pytest.mark.parametrize('rows', [1, 63, 64, 4096, 32768, 35008, 204800, 1000000])
+def test_ws_bytes_of_every_weight_gradient_follow_one_row_split(rows):
+    """The row split every weight-gradient kernel shares: up to 512 workgroups (the cap) of at
+    least 64 rows (the floor), each a whole number of 32-row chunks. The one-pass backwards size
+    their workspace for the workgroups that split launches (one partial row [dW | db] each);
+    rs_wgrad_ws_bytes, which serves the fp32 kernel (16-row chunks) and the bf16 one alike, for
+    the workgroup count before the rounding to whole chunks, which bounds both."""
+    L = _hip.lib()
+    nb = min(max(rows // 64, 1), 512)
+    per_wg = -(-rows // nb)               # rows of a workgroup ...
+    per_wg = -(-per_wg // 32) * 32        # ... in whole 32-row chunks
+    blocks = -(-rows // per_wg)
+    assert blocks <= nb
+    assert L.rs_outproj_bwd_bf16_ws_bytes(rows, 64) == blocks * (64 * 64 + 64) * 4
+    for dcat in (24, 40, 72):
+        assert L.rs_seq_input_bwd_bf16_ws_bytes(rows, 64, dcat) == blocks * (64 * dcat + 64) * 4
+    assert L.rs_linear_bwd_bf16_ws_bytes(rows, 192, 64) == blocks * (192 * 64 + 192) * 4
+    for Mo, No in ((64, 64), (64, 40), (192, 64), (256, 172)):
+        assert L.rs_wgrad_ws_bytes(Mo, No, rows) == nb * (Mo * No + Mo) * 4
+
+
 def test_bad_arguments_are_errors():
     with pytest.raises(_hip.HipError, match='d == 64'):
         _hip.call('rs_outproj_bwd_bf16', None, None, None, 64, 128, 32, 0.0, None, 0, None, None, None, None, None)
