@@ -161,6 +161,45 @@ int rs_gather_bwd(const rs_feature_seg_t* segs, int nseg, int rows, const float*
  * algorithms(True) in the caller switches it on, as it does for torch's own index_add / embedding
  * backward). Returns the previous setting. */
 int rs_set_deterministic(int on);
+/* The launch plan of a gather call, host only (no device, no pointer is followed): the route each
+ * segment takes through rs_gather_fwd (bwd == 0) or rs_gather_bwd (bwd != 0) and its sizing,
+ * planned as rs_gather_ws_bytes plans -- 16-byte-aligned output rows -- under the current
+ * rs_set_deterministic / RSYS_* settings. Either output may be null. */
+#define RS_GATHER_FWD_ROWS 0       /* rows read from HBM / L2 */
+#define RS_GATHER_FWD_STAGED 1     /* the whole table staged into LDS first */
+#define RS_GATHER_FWD_HOT 2        /* RSYS_HOT_ROWS=1: the hot rows of a pooled call staged into LDS */
+#define RS_GATHER_BWD_SCATTER 0    /* float atomics on the table gradient; last-valid / copy rows */
+#define RS_GATHER_BWD_SMALL_LDS 1  /* workgroup-private LDS copy of a small table, then atomics */
+#define RS_GATHER_BWD_SLOT 2       /* deterministic mode: slot-private LDS images */
+#define RS_GATHER_BWD_RANGE 3      /* row-range LDS images over lookup chunks */
+#define RS_GATHER_BWD_ONEHOT 4     /* one-hot MFMA product of a tiny, heavily hit table */
+#define RS_GATHER_BWD_DENSE 5      /* Linear(1, D): column reduction */
+typedef struct rs_gather_seg_plan {
+  int route;                /* RS_GATHER_FWD_* or RS_GATHER_BWD_* */
+  int blocks;               /* workgroups of this segment in its route's launch */
+  int first_block;          /* its first workgroup among that route's segments */
+  int rows_per_block;
+  int lanes_per_row;
+  int bag_split;            /* row groups sharing one pooled bag */
+  int rows_per_lane;
+  int staged_bytes;         /* forward: table bytes staged into LDS */
+  int partial_chunks;       /* backward: [vocab, dim] partials in the workspace (slot, range, one-hot) */
+  int slots;                /* slot route: LDS images per workgroup */
+  int onehot_rows_per_wave;
+  int range_rows;           /* range route: table rows per range */
+  int ranges;
+  int64_t partial_off;      /* floats from the workspace start to this segment's partials */
+} rs_gather_seg_plan_t;
+typedef struct rs_gather_launch_plan {
+  int fwd_lds;              /* dynamic LDS bytes: the forward kernel, */
+  int small_lds;            /* the small-LDS blocks of the fused backward kernel (which takes >= 2 KB), */
+  int range_lds;            /* the range, */
+  int slot_lds;             /* slot */
+  int onehot_lds;           /* and one-hot kernels */
+  int64_t ws_floats;        /* rs_gather_ws_bytes / 4 */
+} rs_gather_launch_plan_t;
+int rs_gather_plan(const rs_feature_seg_t* segs, int nseg, int rows, int ldo, int bwd,
+                   rs_gather_seg_plan_t* out_per_segment, rs_gather_launch_plan_t* out_launch);
 
 /* h = dropout(A W^T + bias) + resid; y = LayerNorm(h)*gamma + beta; per-row mean / rstd.
  * The post-LN residual block of nn.TransformerEncoderLayer (x + dropout(sublayer(x)) -> norm,

@@ -32,6 +32,23 @@ class FeatureSeg(C.Structure):
                 ('lazy_last', vp), ('hot_keys', vp), ('hot_n', i64)]
 
 
+GATHER_FWD_ROUTES = ('rows', 'staged', 'hot')  # RS_GATHER_FWD_*
+GATHER_BWD_ROUTES = ('scatter', 'small_lds', 'slot', 'range', 'onehot', 'dense')  # RS_GATHER_BWD_*
+
+
+class GatherSegPlan(C.Structure):
+    """Mirror of rs_gather_seg_plan_t."""
+    _fields_ = [(n, i32) for n in ('route', 'blocks', 'first_block', 'rows_per_block', 'lanes_per_row', 'bag_split',
+                                   'rows_per_lane', 'staged_bytes', 'partial_chunks', 'slots',
+                                   'onehot_rows_per_wave', 'range_rows', 'ranges')] + [('partial_off', i64)]
+
+
+class GatherLaunchPlan(C.Structure):
+    """Mirror of rs_gather_launch_plan_t."""
+    _fields_ = [(n, i32) for n in ('fwd_lds', 'small_lds', 'range_lds', 'slot_lds', 'onehot_lds')] + \
+               [('ws_floats', i64)]
+
+
 class SortedCall(C.Structure):
     """Mirror of rs_sorted_call_t."""
     _fields_ = [('keys', vp), ('n', i64), ('D', i32), ('call', i32), ('p', vp), ('g', vp), ('m', vp), ('v', vp),
@@ -87,6 +104,7 @@ SIGNATURES = {
     'rs_gather_ws_bytes': (i64, [vp, i32, i32]),
     'rs_gather_bwd': (i32, [vp, i32, i32, vp, i32, vp, vp]),
     'rs_set_deterministic': (i32, [i32]),
+    'rs_gather_plan': (i32, [vp, i32, i32, i32, i32, vp, vp]),
     'rs_seq_mask': (i32, [vp, i64, i32, i32, i64, vp, vp, vp]),
     'rs_attn_fwd': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, i32, vp, vp]),
     'rs_attn_bwd': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, i32, vp, vp]),

@@ -112,9 +112,10 @@ struct SegLaunch {
 };
 static_assert(sizeof(SegLaunch) <= 4096, "SegLaunch must fit the kernel-argument segment");
 
-__device__ __forceinline__ int find_seg(const SegLaunch& a, int bid) {
+// the segment that owns workgroup bid of a launch whose segment s starts at workgroup starts[s]
+__device__ __forceinline__ int find_seg(const int* starts, int nseg, int bid) {
   int s = 0;
-  while (s + 1 < a.nseg && bid >= a.block_start[s + 1]) ++s;
+  while (s + 1 < nseg && bid >= starts[s + 1]) ++s;
   return s;
 }
 
@@ -498,7 +499,7 @@ __device__ void gather_pool_hot(const SegLaunch& a, const rs_feature_seg_t& sg, 
 template <bool LAZY>
 __global__ __launch_bounds__(256) void gather_fwd_kernel(SegLaunch a) {
   extern __shared__ float4 stage_lds[];
-  const int s = find_seg(a, blockIdx.x);
+  const int s = find_seg(a.block_start, a.nseg, blockIdx.x);
   rs_feature_seg_t sg = a.segs[s];
   const int lb = blockIdx.x - a.block_start[s];
   if (LAZY && sg.lazy_last) {  // uniform per workgroup
@@ -647,7 +648,7 @@ __device__ void scatter_seg(const SegLaunch& a, const rs_feature_seg_t& sg, int 
 }
 
 __device__ __forceinline__ void gather_bwd_body(const SegLaunch& a, int bid) {
-  const int s = find_seg(a, bid);
+  const int s = find_seg(a.block_start, a.nseg, bid);
   const rs_feature_seg_t& sg = a.segs[s];
   if (sg.kind == RS_SEG_DENSE || a.small[s]) return;
   const int lb = bid - a.block_start[s];
@@ -668,8 +669,7 @@ __device__ __forceinline__ void gather_bwd_body(const SegLaunch& a, int bid) {
 }
 
 __device__ __forceinline__ void gather_bwd_small_body(const SegLaunch& a, int bid, float* lds) {
-  int s = 0;
-  while (s + 1 < a.nseg && bid >= a.sblock_start[s + 1]) ++s;
+  const int s = find_seg(a.sblock_start, a.nseg, bid);
   const rs_feature_seg_t& sg = a.segs[s];
   const int lb = bid - a.sblock_start[s];
   const int nblk = a.sblocks[s];
@@ -788,8 +788,7 @@ constexpr int kSlotBag = 8;   // bags up to this long load all their ids at once
 
 __global__ __launch_bounds__(256) void gather_bwd_slot_kernel(SegLaunch a) {
   extern __shared__ __attribute__((aligned(16))) float img[];  // [slots][V][D]
-  int s = 0;
-  while (s + 1 < a.nseg && (int)blockIdx.x >= a.tblock_start[s + 1]) ++s;
+  const int s = find_seg(a.tblock_start, a.nseg, blockIdx.x);
   const rs_feature_seg_t& sg = a.segs[s];
   const int lb = blockIdx.x - a.tblock_start[s];
   const int nblk = a.tblocks[s], nsl = a.slots[s];
@@ -876,8 +875,7 @@ template <int MT>
 __global__ __launch_bounds__(kOhWaves * 64) void gather_bwd_onehot_kernel(SegLaunch a) {
   typedef float f4v __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) float red[];  // [4][V * D]
-  int s = 0;
-  while (s + 1 < a.nseg && (int)blockIdx.x >= a.oblock_start[s + 1]) ++s;
+  const int s = find_seg(a.oblock_start, a.nseg, blockIdx.x);
   const rs_feature_seg_t& sg = a.segs[s];
   const int lb = blockIdx.x - a.oblock_start[s];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1001,8 +999,7 @@ __global__ __launch_bounds__(kRangeThreads) void gather_bwd_range_kernel(SegLaun
   extern __shared__ __attribute__((aligned(16))) float lds[];  // the range image [R][D]
   __shared__ __attribute__((aligned(16))) short sid[kRangeIds];
   __shared__ int queue[kRangeWaves][kRangeQueue];
-  int s = 0;
-  while (s + 1 < a.nseg && (int)blockIdx.x >= a.rblock_start[s + 1]) ++s;
+  const int s = find_seg(a.rblock_start, a.nseg, blockIdx.x);
   const rs_feature_seg_t& sg = a.segs[s];
   const int lb = blockIdx.x - a.rblock_start[s];
   const int nr = a.rranges[s], nch = a.rchunks[s];
@@ -1152,50 +1149,97 @@ __global__ __launch_bounds__(kReduceWaves * 64) void reduce_partials_kernel(SegL
   }
 }
 
-// Ranged table-gradient plan of one segment (0 ranges: the atomic scatter). Sparse ids and sum /
-// mean bags of a table of 48 KB - 4 MB (smaller ones: the slot kernel), D in {16, 32, 64, 128,
-// 256} (D/4 lanes per lookup divide a wave into <= 16 groups); ranges of 64 KB; chunks of >= 2 x
-// vocab lookups (the [vocab, dim] partial of a chunk costs no more than its dout rows), a multiple
-// of 8 (XCD mapping), at most 1024 / ranges. Deterministic mode (round 4) also takes the tables hit
-// < 8 times per row (C2's 6,060-row user and 3,500-row item tables at 4,096 lookups) and the
-// small ones the slot kernel leaves to it: measured at C2 (tools/gather_bwd_time.py) the user
-// tower's table gradients 25 -> 53-65 us, so the atomic scatter stays the default for them.
-struct RangePlan { int rows, ranges, chunks; };
+// ---------------------------------------------------------------- launch planning (host only)
+// Every segment takes ONE route through the forward launch and one through the backward's:
+// fwd_route / bwd_route read top to bottom as priority lists over the segment, the row count,
+// whether its rows move as float4 (vec) and the switches. Each route's sizing is a function of its
+// own below; the kernels read the result from SegLaunch.
+enum FwdRoute { kRows = RS_GATHER_FWD_ROWS, kStaged = RS_GATHER_FWD_STAGED, kHot = RS_GATHER_FWD_HOT };
+enum BwdRoute { kScatter = RS_GATHER_BWD_SCATTER, kSmallLds = RS_GATHER_BWD_SMALL_LDS, kSlot = RS_GATHER_BWD_SLOT,
+                kRange = RS_GATHER_BWD_RANGE, kOneHot = RS_GATHER_BWD_ONEHOT, kDense = RS_GATHER_BWD_DENSE };
 
-RangePlan range_plan(const rs_feature_seg_t& g, int rows, bool vec) {
-  RangePlan r{0, 0, 0};
-  const bool table_kind = g.kind == RS_SEG_SPARSE || (g.kind == RS_SEG_POOL && g.pool_mode != RS_POOL_MAX);
-  const bool dim_ok = g.dim >= 16 && g.dim <= 256 && 256 % g.dim == 0;
-  const int64_t tbytes = g.vocab * g.dim * 4;
-  const int64_t n = (int64_t)rows * (g.kind == RS_SEG_POOL ? g.bag : 1);
-  // default: tables hit >= 8 times per row on average (the atomic scatter is faster below that);
-  // deterministic mode: every table of 4 MB or less that the kernel takes, small ones included
-  const bool det = deterministic();
-  if (!table_kind || !vec || !dim_ok || (tbytes <= kSmallTableBytes && !det) || tbytes > (4 << 20) || n == 0 ||
-      (n < 8 * g.vocab && !det) || getenv_flag("RSYS_NO_RANGE_GRAD"))
-    return r;
-  int R = kRangeBytes / (g.dim * 4);
-  const int nr = (int)((g.vocab + R - 1) / R);
-  R = (int)((g.vocab + nr - 1) / nr);  // balanced ranges
-  int nch = (int)(n / (2 * g.vocab)) / 8 * 8;
-  const int one_pass = (cdiv(n, kRangeIds) + 7) / 8 * 8;  // every chunk staged in one pass
-  if (nch < one_pass) nch = one_pass;
-  const int cap = (1024 / nr) / 8 * 8;
-  if (nch > cap) nch = cap;
-  if (nch < 8) nch = 8;
-  r.rows = R;
-  r.ranges = nr;
-  r.chunks = nch;
-  return r;
+// read on every call; det: rs_set_deterministic / RSYS_DETERMINISTIC
+struct Switches { bool det, no_range, no_onehot, no_stage, hot_rows; };
+Switches switches() {
+  return {deterministic(), getenv_flag("RSYS_NO_RANGE_GRAD"), getenv_flag("RSYS_NO_ONEHOT_GRAD"),
+          getenv_flag("RSYS_NO_LDS_STAGE"), getenv_flag("RSYS_HOT_ROWS")};
 }
 
-int plan(SegLaunch& a, const rs_feature_seg_t* segs_host, int nseg, int rows, int ldo,
-         const float* out_ptr_for_align, bool bwd = false) {
+bool is_table(const rs_feature_seg_t& g) { return g.kind == RS_SEG_SPARSE || g.kind == RS_SEG_POOL; }
+bool max_pooled(const rs_feature_seg_t& g) { return g.kind == RS_SEG_POOL && g.pool_mode == RS_POOL_MAX; }
+bool sum_pooled(const rs_feature_seg_t& g) { return g.kind == RS_SEG_POOL && g.pool_mode != RS_POOL_MAX; }  // or mean
+int64_t lookups(const rs_feature_seg_t& g, int rows) { return (int64_t)rows * (g.kind == RS_SEG_POOL ? g.bag : 1); }
+int64_t table_bytes(const rs_feature_seg_t& g) { return g.vocab * g.dim * 4; }
+// rows the ranged kernel takes: float4 slices, D/4 lanes per lookup dividing a wave into <= 16 groups
+bool rangeable(const rs_feature_seg_t& g, bool vec) { return vec && g.dim >= 16 && g.dim <= 256 && 256 % g.dim == 0; }
+
+// rpb: the rows a workgroup of the plain launch reads
+FwdRoute fwd_route(const rs_feature_seg_t& g, bool vec, int rpb, const Switches& sw) {
+  if (!is_table(g) || !vec || g.lazy_last) return kRows;
+  // opt-in: sum / mean bags with their sorted call, the hot rows staged per persistent workgroup
+  if (sum_pooled(g) && g.hot_keys && g.hot_n >= 2 * kHotQ && g.dim <= 256 && sw.hot_rows) return kHot;
+  // a table of <= kStageBytes whose workgroup reads at least as many row bytes as the table holds
+  if (table_bytes(g) <= kStageBytes && table_bytes(g) <= lookups(g, rpb) * g.dim * 4 && !sw.no_stage) return kStaged;
+  return kRows;
+}
+
+BwdRoute bwd_route(const rs_feature_seg_t& g, int rows, bool vec, const Switches& sw) {
+  if (g.kind == RS_SEG_DENSE) return kDense;  // Linear(1, D): the column reduction
+  if (!is_table(g)) return kScatter;          // last-valid rows, slice copies: plain adds / stores
+  const bool small = table_bytes(g) <= kSmallTableBytes;
+  // a max-pooled table's arg-max needs the table rows: float atomics in both modes
+  if (max_pooled(g)) return small ? kSmallLds : kScatter;
+  // tiny, heavily hit tables, both modes (RSYS_NO_ONEHOT_GRAD=1: the routes below)
+  if (g.vocab <= 16 * kOhMaxM && g.dim <= 16 && g.vocab * g.dim <= kOhMaxE && lookups(g, rows) >= kOhMinLookups &&
+      !sw.no_onehot)
+    return kOneHot;
+  // deterministic mode, small tables: slot images where >= 4 slots fit (<= 16 KB) or the ranged
+  // kernel cannot take the rows; the larger ones it takes (C2 / C3's zip table) fall through to it
+  if (sw.det && small && g.dim <= 64 && (table_bytes(g) <= 16 * 1024 || !rangeable(g, vec))) return kSlot;
+  if (small && !(sw.det && rangeable(g, vec))) return kSmallLds;
+  // up to 4 MB: hit >= 8 times per row on average (the atomic scatter is faster below that: C2's
+  // 6,060-row user and 3,500-row item tables at 4,096 lookups, 25 -> 53-65 us ranged,
+  // tools/gather_bwd_time.py); deterministic mode: every such table
+  if (rangeable(g, vec) && table_bytes(g) <= (4 << 20) && (sw.det || lookups(g, rows) >= 8 * g.vocab) && !sw.no_range)
+    return kRange;
+  return kScatter;
+}
+
+struct SegRoute { int route, blocks, first_block; };  // blocks: workgroups in the route's launch
+struct Plan { SegLaunch a; SegRoute seg[kMaxSeg]; int ndense; };
+
+// starts[s]: the first workgroup of segment s in the launch of `route` (route < 0: every segment is
+// in it), segments in order; starts[nseg]: the launch's workgroups. Sets first_block of its segments.
+void block_starts(Plan& pl, int route, int* starts) {
+  int b = 0;
+  for (int s = 0; s < pl.a.nseg; ++s) {
+    starts[s] = b;
+    if (route >= 0 && pl.seg[s].route != route) continue;
+    pl.seg[s].first_block = b;
+    b += pl.seg[s].blocks;
+  }
+  starts[pl.a.nseg] = b;
+}
+
+// Split long sum / mean bags over S row groups while the launch is short of ~8 waves per SIMD
+// and every group keeps >= 8 positions (C3: B = 4096, L = 50, D = 128 -> S = 4).
+// (round 5 measured non-temporal row loads for large tables slower in the step, C3 fp32 0.037
+// -> 0.043 ms: the catch-up has just brought the rows on chip)
+int bag_split(const rs_feature_seg_t& g, int rows, int C) {
+  int S = 1;
+  while (sum_pooled(g) && 2 * S * C <= 256 && (g.bag + 2 * S - 1) / (2 * S) >= 8 && (int64_t)rows * C * S < 8192 * 64)
+    S *= 2;
+  return S;
+}
+
+// The argument checks and what both directions share: vec and the lanes per row.
+int plan_common(Plan& pl, const rs_feature_seg_t* segs, int nseg, int rows, int ldo, const float* out_ptr_for_align) {
   RS_CHECK_ARG(nseg >= 1 && nseg <= kMaxSeg, "gather: nseg %d out of [1,%d]", nseg, kMaxSeg);
-  int blocks = 0;
-  a.stage_lds = 0;
+  pl = Plan{};
+  SegLaunch& a = pl.a;
+  a.nseg = nseg; a.rows = rows; a.ldo = ldo;
   for (int s = 0; s < nseg; ++s) {
-    const rs_feature_seg_t& g = segs_host[s];
+    const rs_feature_seg_t& g = segs[s];
     RS_CHECK_ARG(g.dim >= 1 && g.dim <= 1024, "gather: seg %d dim %d", s, g.dim);
     RS_CHECK_ARG(g.out_col >= 0 && g.out_col + g.dim <= ldo, "gather: seg %d columns exceed ldo", s);
     RS_CHECK_ARG(g.kind >= 0 && g.kind <= 4, "gather: seg %d bad kind %d", s, g.kind);
@@ -1208,162 +1252,123 @@ int plan(SegLaunch& a, const rs_feature_seg_t* segs_host, int nseg, int rows, in
     RS_CHECK_ARG(C <= 256, "gather: seg %d too wide", s);
     a.vec[s] = vec;
     a.chunks[s] = C;
-    const bool table_kind = g.kind == RS_SEG_SPARSE || g.kind == RS_SEG_POOL;
-    // small tables: the float-atomic small-table kernel by default; deterministic mode
-    // (rs_set_deterministic): the slot-image kernel where >= 4 slots fit (images <= 16 KB), the
-    // ranged kernel for the larger ones it takes (D >= 16, float4 rows: C2 / C3's zip table),
-    // else slots anyway. A max-pooled table (its arg-max needs the table rows) keeps the atomics.
-    const bool det = bwd && deterministic();
-    const int64_t tb = g.vocab * g.dim * 4;
-    const bool rangeable = vec && g.dim >= 16 && g.dim <= 256 && 256 % g.dim == 0;
-    // tiny tables (both modes): the one-hot MFMA kernel (RSYS_NO_ONEHOT_GRAD=1: the kernels below)
-    a.oh[s] = bwd && table_kind && !(g.kind == RS_SEG_POOL && g.pool_mode == RS_POOL_MAX) && g.vocab <= 16 * kOhMaxM &&
-              g.dim <= 16 && g.vocab * g.dim <= kOhMaxE &&
-              (int64_t)rows * (g.kind == RS_SEG_POOL ? g.bag : 1) >= kOhMinLookups && !getenv_flag("RSYS_NO_ONEHOT_GRAD");
-    a.tiny[s] = det && table_kind && !(g.kind == RS_SEG_POOL && g.pool_mode == RS_POOL_MAX) && !a.oh[s] &&
-               tb <= kSmallTableBytes && g.dim <= 64 && (tb <= 16 * 1024 || !rangeable);
-    a.small[s] = bwd && table_kind && tb <= kSmallTableBytes && !a.tiny[s] && !a.oh[s] && !(det && rangeable &&
-               !(g.kind == RS_SEG_POOL && g.pool_mode == RS_POOL_MAX));
-    // Split long sum/mean bags over S row groups while the launch is short of ~8 waves per SIMD
-    // and every group keeps >= 8 positions (C3: B = 4096, L = 50, D = 128 -> S = 4).
-    int S = 1;
-    // (round 5 measured non-temporal row loads for large tables slower in the step, C3 fp32 0.037
-    // -> 0.043 ms: the catch-up has just brought the rows on chip)
-    if (g.kind == RS_SEG_POOL && g.pool_mode != RS_POOL_MAX && !a.small[s]) {
-      while (2 * S * C <= 256 && (g.bag + 2 * S - 1) / (2 * S) >= 8 &&
-             (int64_t)rows * C * S < 8192 * 64)
-        S *= 2;
-    }
-    a.split[s] = S;
-    // token-sized sparse forward launches: kRowsPerLane rows per lane (>= 2048 workgroups otherwise)
-    a.rpt[s] = (!bwd && vec && g.kind == RS_SEG_SPARSE && (int64_t)rows * C >= (int64_t)2048 * 256)
-                   ? kRowsPerLane : 1;
-    a.rpb[s] = 256 / (C * S);
-    a.hot[s] = !bwd && vec && g.kind == RS_SEG_POOL && g.pool_mode != RS_POOL_MAX && g.hot_keys &&
-               g.hot_n >= 2 * kHotQ && !g.lazy_last && g.dim <= 256 && getenv_flag("RSYS_HOT_ROWS");
-    if (a.hot[s]) {
-      const int hb = kHotMax * g.dim * 4;
-      if (hb > a.stage_lds) a.stage_lds = hb;
-    }
-    a.stage[s] = 0;
-    if (!bwd && table_kind && vec && !a.hot[s]) {
-      const int64_t tbytes = g.vocab * g.dim * 4;
-      const int64_t read = (int64_t)a.rpb[s] * (g.kind == RS_SEG_POOL ? g.bag : 1) * g.dim * 4;
-      if (tbytes <= kStageBytes && tbytes <= read && !g.lazy_last && !getenv_flag("RSYS_NO_LDS_STAGE")) {
-        a.stage[s] = (int)tbytes;
-        if (a.stage[s] > a.stage_lds) a.stage_lds = a.stage[s];
-      }
-    }
-    a.rranges[s] = 0;
-    a.rchunks[s] = 0;
-    a.rrows[s] = 0;
-    if (bwd && !a.small[s] && !a.tiny[s] && !a.oh[s]) {
-      const RangePlan rp = range_plan(g, rows, vec);
-      a.rrows[s] = rp.rows;
-      a.rranges[s] = rp.ranges;
-      a.rchunks[s] = rp.chunks;
-    }
-    a.block_start[s] = blocks;
-    if (a.hot[s]) {
-      const int ng = cdiv(rows, a.rpb[s]);
-      blocks += ng < kHotBlocks ? ng : kHotBlocks;
-    } else if (!a.small[s] && !a.rranges[s] && !a.tiny[s] && !a.oh[s] && !(bwd && g.kind == RS_SEG_DENSE)) {
-      blocks += cdiv(rows, a.rpb[s] * a.rpt[s]);
-    }
   }
-  a.block_start[nseg] = blocks;
-  int rb = 0;
-  a.range_lds = 0;
-  for (int s = 0; s < nseg; ++s) {
-    a.rblock_start[s] = rb;
-    if (a.rranges[s]) {
-      rb += a.rranges[s] * a.rchunks[s];
-      const int bytes = a.rrows[s] * segs_host[s].dim * 4;
-      if (bytes > a.range_lds) a.range_lds = bytes;
-    }
-  }
-  a.rblock_start[nseg] = rb;
-  int ob = 0;
-  a.slot_lds = 0;
-  for (int s = 0; s < nseg; ++s) {
-    a.tblock_start[s] = ob;
-    a.tblocks[s] = 0;
-    a.slots[s] = 0;
-    if (a.tiny[s]) {
-      // slots: as many D-lane groups as a workgroup holds, within 64 KB of images; workgroups:
-      // >= kSlotRowsInFlight rows per slot, <= 256, and <= 4 MB of partials in all
-      const int64_t E = segs_host[s].vocab * segs_host[s].dim;
-      int nsl = 256 / segs_host[s].dim;
-      const int fit = (int)((64 * 1024) / (E * 4));
-      nsl = nsl < fit ? nsl : fit;
-      nsl = nsl < 1 ? 1 : nsl;
-      // one batch of kSlotRows rows per slot where the grid allows (<= 2048 workgroups, <= 8 MB
-      // of partials): the kernel is a single round trip of loads per workgroup
-      int64_t nb = cdiv(rows, nsl * kSlotRows);
-      const int64_t cap = std::max<int64_t>(8, (8ll << 20) / (E * 4));
-      nb = std::min<int64_t>(std::min<int64_t>(nb, 2048), cap);
-      a.slots[s] = (int16_t)nsl;
-      a.tblocks[s] = (int16_t)(nb < 1 ? 1 : nb);
-      ob += a.tblocks[s];
-      a.slot_lds = std::max<int>(a.slot_lds, (int)(nsl * E * 4));
-    }
-  }
-  a.tblock_start[nseg] = ob;
-  // one-hot tables: workgroups of 8 waves, each wave a run of whole 32-row batches (C2's
-  // genre tokens: 200 workgroups of 4 batches a wave, 26.2 us a call against 27.3 at 400 x 2 and
-  // 35.0 at 800 x 1 -- the partials and workgroup launches cost more than the batch round trips)
-  int hb = 0;
-  a.oh_lds = 0;
-  for (int s = 0; s < nseg; ++s) {
-    a.oblock_start[s] = hb;
-    a.oh_rpw[s] = 0;
-    if (!a.oh[s]) continue;
-    const int64_t per_wave_min = 4 * kOhSteps;
-    // <= 128 rows (4 batches) a wave once the grid is past 256 workgroups (C5's 819,200 history
-    // tokens: 800 workgroups rather than 13 serial batches a wave)
-    int64_t nb = std::max<int64_t>(std::min<int64_t>(256, cdiv(rows, kOhWaves * per_wave_min)),
-                                   std::min<int64_t>(1024, cdiv(rows, kOhWaves * 128)));
-    nb = std::max<int64_t>(1, nb);
-    int64_t rpw = cdiv(cdiv(rows, nb * kOhWaves), per_wave_min) * per_wave_min;
-    nb = std::max<int64_t>(1, cdiv(rows, rpw * kOhWaves));
-    a.oh_rpw[s] = (int)rpw;
-    a.tblocks[s] = (int16_t)nb;  // the partial count (pchunks)
-    hb += (int)nb;
-    a.oh_lds = std::max<int>(a.oh_lds, (int)(4 * segs_host[s].vocab * segs_host[s].dim * 4));
-  }
-  a.oblock_start[nseg] = hb;
-  a.ws = nullptr;
+  return 0;
+}
 
-  int sb = 0;
-  a.small_lds = 0;
+int plan_fwd(Plan& pl, const rs_feature_seg_t* segs, int nseg, int rows, int ldo, const float* out) {
+  RS_RET_IF(plan_common(pl, segs, nseg, rows, ldo, out));
+  SegLaunch& a = pl.a;
+  const Switches sw = switches();
   for (int s = 0; s < nseg; ++s) {
-    a.sblock_start[s] = sb;
-    a.sblocks[s] = 0;
-    if (a.small[s]) {
-      const int64_t work = (int64_t)rows * (segs_host[s].kind == RS_SEG_POOL ? segs_host[s].bag : 1);
-      // ~256 lookups per workgroup: enough workgroups that the LDS accumulation is not one
-      // long serial chain; each flushes only its non-zero table entries
-      int nb = (int)(work / 256);
-      nb = nb < 1 ? 1 : (nb > 512 ? 512 : nb);
-      const int maxnb = cdiv(rows, a.rpb[s]);
-      a.sblocks[s] = nb < maxnb ? nb : maxnb;
-      sb += a.sblocks[s];
-      const int bytes = (int)(segs_host[s].vocab * segs_host[s].dim * 4);
-      if (bytes > a.small_lds) a.small_lds = bytes;
+    const rs_feature_seg_t& g = segs[s];
+    const int C = a.chunks[s];
+    a.split[s] = bag_split(g, rows, C);
+    a.rpb[s] = 256 / (C * a.split[s]);
+    // token-sized sparse launches: kRowsPerLane rows per lane (>= 2048 workgroups otherwise)
+    a.rpt[s] = (a.vec[s] && g.kind == RS_SEG_SPARSE && (int64_t)rows * C >= (int64_t)2048 * 256) ? kRowsPerLane : 1;
+    const int route = pl.seg[s].route = fwd_route(g, a.vec[s], a.rpb[s], sw);
+    pl.seg[s].blocks = cdiv(rows, a.rpb[s] * a.rpt[s]);
+    if (route == kHot) {
+      a.hot[s] = 1;
+      pl.seg[s].blocks = std::min(cdiv(rows, a.rpb[s]), kHotBlocks);
+      a.stage_lds = std::max(a.stage_lds, kHotMax * g.dim * 4);
+    } else if (route == kStaged) {
+      a.stage[s] = (int)table_bytes(g);
+      a.stage_lds = std::max(a.stage_lds, a.stage[s]);
     }
   }
-  a.sblock_start[nseg] = sb;
+  block_starts(pl, -1, a.block_start);
+  return 0;
+}
+
+// kSmallLds: ~256 lookups per workgroup: enough workgroups that the LDS accumulation is not one
+// long serial chain; each flushes only its non-zero table entries
+void size_small(SegLaunch& a, SegRoute& r, int s, const rs_feature_seg_t& g, int rows) {
+  const int nb = (int)std::min<int64_t>(std::max<int64_t>(lookups(g, rows) / 256, 1), 512);
+  a.small[s] = 1;
+  a.sblocks[s] = r.blocks = std::min(nb, cdiv(rows, a.rpb[s]));
+  a.small_lds = std::max(a.small_lds, (int)table_bytes(g));
+}
+
+// kSlot: as many D-lane groups (slots) as a workgroup holds, within 64 KB of images; one batch of
+// kSlotRows rows per slot where the grid allows (<= 2048 workgroups, <= 8 MB of partials): the
+// kernel is a single round trip of loads per workgroup
+void size_slot(SegLaunch& a, SegRoute& r, int s, const rs_feature_seg_t& g, int rows) {
+  const int64_t E = g.vocab * g.dim;
+  const int nsl = std::max(1, std::min(256 / g.dim, (int)((64 * 1024) / (E * 4))));
+  const int64_t cap = std::max<int64_t>(8, (8ll << 20) / (E * 4));
+  const int64_t nb = std::min<int64_t>(std::min<int64_t>(cdiv(rows, nsl * kSlotRows), 2048), cap);
+  a.tiny[s] = 1;
+  a.slots[s] = (int16_t)nsl;
+  r.blocks = a.tblocks[s] = a.pchunks[s] = (int16_t)std::max<int64_t>(nb, 1);
+  a.slot_lds = std::max(a.slot_lds, (int)(nsl * E * 4));
+}
+
+// kOneHot: workgroups of 8 waves, each wave a run of whole 32-row batches (C2's genre tokens:
+// 200 workgroups of 4 batches a wave, 26.2 us a call against 27.3 at 400 x 2 and 35.0 at 800 x 1
+// -- the partials and workgroup launches cost more than the batch round trips); <= 128 rows (4
+// batches) a wave once the grid is past 256 workgroups (C5's 819,200 history tokens: 800
+// workgroups rather than 13 serial batches a wave)
+void size_onehot(SegLaunch& a, SegRoute& r, int s, const rs_feature_seg_t& g, int rows) {
+  const int64_t per_wave_min = 4 * kOhSteps;
+  int64_t nb = std::max<int64_t>(std::min<int64_t>(256, cdiv(rows, kOhWaves * per_wave_min)),
+                                 std::min<int64_t>(1024, cdiv(rows, kOhWaves * 128)));
+  nb = std::max<int64_t>(1, nb);
+  const int64_t rpw = cdiv(cdiv(rows, nb * kOhWaves), per_wave_min) * per_wave_min;
+  nb = std::max<int64_t>(1, cdiv(rows, rpw * kOhWaves));
+  a.oh[s] = 1;
+  a.oh_rpw[s] = (int)rpw;
+  r.blocks = a.tblocks[s] = a.pchunks[s] = (int16_t)nb;  // one partial per workgroup
+  a.oh_lds = std::max(a.oh_lds, (int)(4 * table_bytes(g)));
+}
+
+// kRange: balanced ranges of <= 64 KB; chunks of >= 2 x vocab lookups (the [vocab, dim] partial
+// of a chunk costs no more than its dout rows), each staged in one pass, a multiple of 8 (XCD
+// mapping), at most 1024 / ranges
+void size_range(SegLaunch& a, SegRoute& r, int s, const rs_feature_seg_t& g, int rows) {
+  const int64_t n = lookups(g, rows);
+  const int nr = cdiv(g.vocab, kRangeBytes / (g.dim * 4));
+  int nch = (int)(n / (2 * g.vocab)) / 8 * 8;
+  nch = std::max(nch, (cdiv(n, kRangeIds) + 7) / 8 * 8);
+  nch = std::max(std::min(nch, (1024 / nr) / 8 * 8), 8);
+  a.rrows[s] = cdiv(g.vocab, nr);
+  a.rranges[s] = (int16_t)nr;
+  a.rchunks[s] = a.pchunks[s] = (int16_t)nch;
+  r.blocks = nr * nch;
+  a.range_lds = std::max(a.range_lds, a.rrows[s] * g.dim * 4);
+}
+
+int plan_bwd(Plan& pl, const rs_feature_seg_t* segs, int nseg, int rows, int ldo, const float* dout) {
+  RS_RET_IF(plan_common(pl, segs, nseg, rows, ldo, dout));
+  SegLaunch& a = pl.a;
+  const Switches sw = switches();
   int64_t off = 0;
   for (int s = 0; s < nseg; ++s) {
-    a.pchunks[s] = a.rranges[s] ? a.rchunks[s] : ((a.tiny[s] || a.oh[s]) ? a.tblocks[s] : 0);
+    const rs_feature_seg_t& g = segs[s];
+    SegRoute& r = pl.seg[s];
+    r.route = bwd_route(g, rows, a.vec[s], sw);
+    a.split[s] = r.route == kSmallLds ? 1 : bag_split(g, rows, a.chunks[s]);
+    a.rpb[s] = 256 / (a.chunks[s] * a.split[s]);
+    a.rpt[s] = 1;
+    switch (r.route) {
+      case kScatter: r.blocks = cdiv(rows, a.rpb[s]); break;
+      case kSmallLds: size_small(a, r, s, g, rows); break;
+      case kSlot: size_slot(a, r, s, g, rows); break;
+      case kRange: size_range(a, r, s, g, rows); break;
+      case kOneHot: size_onehot(a, r, s, g, rows); break;
+      default: r.blocks = 1; r.first_block = pl.ndense++; break;  // kDense: one workgroup each
+    }
+    // partials [pchunks][vocab][dim] at ws + pws_off, float4-aligned
     a.pws_off[s] = off;
-    off += (int64_t)a.pchunks[s] * segs_host[s].vocab * segs_host[s].dim;
-    off = (off + 3) / 4 * 4;  // float4-aligned partials
+    off = (off + (int64_t)a.pchunks[s] * g.vocab * g.dim + 3) / 4 * 4;
   }
   a.ws_floats = off;
-  a.nseg = nseg;
-  a.rows = rows;
-  a.ldo = ldo;
+  block_starts(pl, kScatter, a.block_start);
+  block_starts(pl, kSmallLds, a.sblock_start);
+  block_starts(pl, kSlot, a.tblock_start);
+  block_starts(pl, kRange, a.rblock_start);
+  block_starts(pl, kOneHot, a.oblock_start);
   return 0;
 }
 
@@ -1396,10 +1401,10 @@ using namespace rs;
 extern "C" int rs_gather_fwd(const rs_feature_seg_t* segs, int nseg, int rows, float* out, int ldo,
                              int* err_flag, void* stream) {
   RS_CHECK_ARG(segs && out, "rs_gather_fwd: null pointer");
-  const rs_feature_seg_t* segs_host = segs;
   if (rows == 0) return 0;
-  SegLaunch a;
-  RS_RET_IF(plan(a, segs_host, nseg, rows, ldo, out));
+  Plan pl;
+  RS_RET_IF(plan_fwd(pl, segs, nseg, rows, ldo, out));
+  SegLaunch& a = pl.a;
   for (int i = 0; i < nseg; ++i) a.segs[i] = segs[i];
   a.out = out; a.dout = nullptr; a.err = err_flag;
   gather_fwd_kernel<false><<<a.block_start[nseg], 256, a.stage_lds, as_stream(stream)>>>(a);
@@ -1413,12 +1418,13 @@ extern "C" int rs_gather_fwd_lazy(const rs_feature_seg_t* segs, int nseg, int ro
                                   void* stream) {
   RS_CHECK_ARG(segs && out && step && consts, "rs_gather_fwd_lazy: null pointer");
   if (rows == 0) return 0;
-  SegLaunch a;
-  RS_RET_IF(plan(a, segs, nseg, rows, ldo, out));
+  Plan pl;
+  RS_RET_IF(plan_fwd(pl, segs, nseg, rows, ldo, out));
+  SegLaunch& a = pl.a;
   for (int i = 0; i < nseg; ++i) {
     const rs_feature_seg_t& g = segs[i];
     if (!g.lazy_last) continue;
-    RS_CHECK_ARG(g.kind == RS_SEG_SPARSE || (g.kind == RS_SEG_POOL && g.pool_mode != RS_POOL_MAX),
+    RS_CHECK_ARG(is_table(g) && !max_pooled(g),
                  "rs_gather_fwd_lazy: seg %d: read-through needs a sparse or sum / mean pooled lookup", i);
     RS_CHECK_ARG(!a.stage[i], "rs_gather_fwd_lazy: seg %d: a read-through table cannot be staged", i);
   }
@@ -1433,21 +1439,34 @@ extern "C" int rs_gather_fwd_lazy(const rs_feature_seg_t* segs, int nseg, int ro
   return 0;
 }
 
-// rs_gather_bwd's workspace: the small and ranged tables' partials. Planned with float4-aligned
-// dout rows (the condition under which a segment is ranged at all): an upper bound.
 extern "C" int rs_set_deterministic(int on) {
   return g_deterministic.exchange(on ? 1 : 0);
 }
 
+extern "C" int rs_gather_plan(const rs_feature_seg_t* segs, int nseg, int rows, int ldo, int bwd,
+                              rs_gather_seg_plan_t* out_per_segment, rs_gather_launch_plan_t* out_launch) {
+  RS_CHECK_ARG(segs && rows >= 1, "rs_gather_plan: bad args");
+  alignas(16) static const float aligned_rows[4] = {0.f, 0.f, 0.f, 0.f};
+  Plan pl;
+  RS_RET_IF(bwd ? plan_bwd(pl, segs, nseg, rows, ldo, aligned_rows) : plan_fwd(pl, segs, nseg, rows, ldo, aligned_rows));
+  const SegLaunch& a = pl.a;
+  for (int s = 0; out_per_segment && s < nseg; ++s)
+    out_per_segment[s] = {pl.seg[s].route, pl.seg[s].blocks, pl.seg[s].first_block, a.rpb[s], a.chunks[s], a.split[s],
+                          a.rpt[s], a.stage[s], a.pchunks[s], a.slots[s], a.oh_rpw[s], a.rrows[s], a.rranges[s],
+                          a.pws_off[s]};
+  if (out_launch) *out_launch = {a.stage_lds, a.small_lds, a.range_lds, a.slot_lds, a.oh_lds, a.ws_floats};
+  return 0;
+}
+
+// rs_gather_bwd's workspace: the slot, one-hot and ranged tables' partials. Planned with float4-
+// aligned dout rows (the condition under which a segment is ranged at all): an upper bound.
 extern "C" int64_t rs_gather_ws_bytes(const rs_feature_seg_t* segs_host, int nseg, int rows) {
   if (!segs_host || nseg < 1 || nseg > kMaxSeg || rows <= 0) return 0;
   int ldo = 4;
   for (int s = 0; s < nseg; ++s) ldo = std::max(ldo, segs_host[s].out_col + segs_host[s].dim);
   ldo = (ldo + 3) / 4 * 4;
-  SegLaunch a;
-  alignas(16) static const float dummy[4] = {0.f, 0.f, 0.f, 0.f};
-  if (plan(a, segs_host, nseg, rows, ldo, dummy, true) != 0) return 0;
-  return a.ws_floats * 4;
+  rs_gather_launch_plan_t lp;
+  return rs_gather_plan(segs_host, nseg, rows, ldo, 1, nullptr, &lp) == 0 ? lp.ws_floats * 4 : 0;
 }
 
 extern "C" int rs_gather_bwd(const rs_feature_seg_t* segs, int nseg, int rows, const float* dout,
@@ -1455,21 +1474,20 @@ extern "C" int rs_gather_bwd(const rs_feature_seg_t* segs, int nseg, int rows, c
   RS_CHECK_ARG(segs && dout, "rs_gather_bwd: null pointer");
   const rs_feature_seg_t* segs_host = segs;
   if (rows == 0) return 0;
-  SegLaunch a;
-  RS_RET_IF(plan(a, segs_host, nseg, rows, ldo, dout, true));
+  Plan pl;
+  RS_RET_IF(plan_bwd(pl, segs_host, nseg, rows, ldo, dout));
+  SegLaunch& a = pl.a;
   for (int s = 0; s < nseg; ++s) {
     const rs_feature_seg_t& g = segs_host[s];
     RS_CHECK_ARG(g.grad, "rs_gather_bwd: seg %d has no grad destination", s);
     RS_CHECK_ARG(g.kind != RS_SEG_DENSE || g.grad_bias, "rs_gather_bwd: seg %d has no bias grad", s);
   }
   for (int i = 0; i < nseg; ++i) a.segs[i] = segs[i];
-  a.out = nullptr; a.dout = dout; a.err = nullptr;
-  a.ws = ws;
+  a.out = nullptr; a.dout = dout; a.err = nullptr; a.ws = ws;
   RS_CHECK_ARG(ws || a.ws_floats == 0,
                "rs_gather_bwd: small / ranged table gradients need ws (rs_gather_ws_bytes)");
   hipStream_t st = as_stream(stream);
-  int ndense = 0;
-  for (int s = 0; s < nseg; ++s) ndense += segs_host[s].kind == RS_SEG_DENSE;
+  const int ndense = pl.ndense;
   if (a.block_start[nseg] + a.sblock_start[nseg] + ndense > 0) {
     gather_bwd_fused_kernel<<<a.sblock_start[nseg] + ndense + a.block_start[nseg], 256,
                               std::max(a.small_lds, 512 * 4), st>>>(a, a.sblock_start[nseg], ndense);

@@ -301,6 +301,14 @@ def segments_array(segs):
     return arr
 
 
+def gather_plan(segs, rows, ldo, bwd):
+    """rs_gather_plan (host only): the per-segment _hip.GatherSegPlan array and the
+    _hip.GatherLaunchPlan of a gather_fwd / gather_bwd call."""
+    per, launch = (_hip.GatherSegPlan * len(segs))(), _hip.GatherLaunchPlan()
+    call('rs_gather_plan', segments_array(segs), len(segs), rows, ldo, int(bwd), per, _hip.C.byref(launch))
+    return per, launch
+
+
 def gather_fwd(segs, rows, out, err_flag=None, lazy=None):
     """rs_gather_fwd; with `lazy` = (m_off, v_off, step, consts, b1, b2, eps, wd) the segments
     whose lazy_last is set read their rows through the lazy-Adam catch-up (rs_gather_fwd_lazy)."""

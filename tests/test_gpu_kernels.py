@@ -239,6 +239,10 @@ def test_gather_backward_matches_embedding_backward(V):
     assert (g[0] == 0).all()
 
 
+def _bwd_routes(segs, rows, ldo):
+    return [_hip.GATHER_BWD_ROUTES[p.route] for p in ops.gather_plan(segs, rows, ldo, 1)[0]]
+
+
 @pytest.mark.parametrize('V,D,rows,Lb,mode', [(3500, 32, 204800, 1, None), (5001, 64, 50000, 1, None),
                                                (3000, 16, 20000, 20, 'mean'), (2000, 8, 9000, 7, 'sum'),
                                                (70000, 4, 600000, 1, None), (30, 8, 204800, 3, 'mean'),
@@ -275,6 +279,11 @@ def test_gather_backward_ranged_hot_tables(monkeypatch, V, D, rows, Lb, mode):
     onehot = V <= 64 and D <= 16 and n >= 65536  # gather_bwd_onehot_kernel, both modes
     assert (L.rs_gather_ws_bytes(arr, 1, rows) > 0) == (ranged or onehot)  # partials in ws
     det_ok = V * D * 4 <= 4 << 20 and (D >= 16 or V * D * 4 <= 48 * 1024)  # slot, ranged or one-hot
+    # the route rs_gather_plan names: (default, deterministic mode)
+    routes = {(3500, 32): ('range', 'range'), (5001, 64): ('range', 'range'), (3000, 16): ('range', 'range'),
+              (2000, 8): ('scatter', 'scatter'), (70000, 4): ('scatter', 'scatter'), (30, 8): ('onehot', 'onehot'),
+              (25, 8): ('small_lds', 'slot'), (700, 16): ('small_lds', 'range'), (3, 4): ('small_lds', 'slot'),
+              (40, 64): ('small_lds', 'slot')}[V, D]
     grads = []
     # the planned path, deterministic mode twice, the atomic scatter
     for off, det in (('', 0), ('', 1), ('', 1), ('1', 0)):
@@ -284,6 +293,8 @@ def test_gather_backward_ranged_hot_tables(monkeypatch, V, D, rows, Lb, mode):
             ops.sync_deterministic()
             if det:
                 assert (L.rs_gather_ws_bytes(arr, 1, rows) > 0) == det_ok
+            route = _bwd_routes([_seg(**seg)], rows, ldo)[0]
+            assert route == ('scatter' if off and routes[det] == 'range' else routes[det])
             g = torch.full((V, D), 0.25, device=DEV)
             ops.gather_bwd([_seg(**seg, grad=g.data_ptr())], rows, dout)
             torch.cuda.synchronize()
@@ -338,6 +349,7 @@ def test_gather_backward_onehot_tiny_tables(monkeypatch, V, D, rows, Lb, mode):
     grads = []
     for off in ('', '', '1'):
         monkeypatch.setenv('RSYS_NO_ONEHOT_GRAD', off)
+        assert _bwd_routes([_seg(**seg)], rows, ldo)[0] == ('small_lds' if off else 'onehot')
         g = torch.full((V, D), 0.5, device=DEV)
         ops.gather_bwd([_seg(**seg, grad=g.data_ptr())], rows, dout)
         torch.cuda.synchronize()
@@ -354,6 +366,68 @@ def test_gather_backward_onehot_tiny_tables(monkeypatch, V, D, rows, Lb, mode):
     g = torch.zeros(V, D, device=DEV)
     ops.gather_bwd([_seg(**dict(seg, idx=bad.data_ptr()), grad=g.data_ptr())], rows, dout)
     assert torch.isfinite(g).all()
+
+
+def test_gather_backward_all_routes_one_launch():
+    """One rs_gather_bwd call whose segments take every backward route between default and
+    deterministic mode (rs_gather_plan names them): the smallest launch in which the per-route
+    workgroup offsets and workspace offsets of different routes sit side by side. Table gradients
+    against the embedding backward, the dense segment against a float64 column reduction (bound:
+    fp32 summation of rows / 32 + 32 terms deep, the kernel's row-lane chains and its tree);
+    deterministic mode bitwise reproducible on every route but the atomic scatter."""
+    rows, ldo, dcol = 22016, 60, 52
+    tables = [(70000, 4, 1), (700, 16, 1), (800, 16, 1), (30, 8, 3), (25, 8, 1)]  # V, D, bag (sum-pooled when > 1)
+    want = {False: ['scatter', 'small_lds', 'range', 'onehot', 'small_lds', 'dense'],
+            True: ['scatter', 'range', 'range', 'onehot', 'slot', 'dense']}
+    dout = rnd(rows, ldo, seed=52)
+    x, w, b = rnd(rows, 1, seed=53), rnd(8, seed=54), rnd(8, seed=55)
+    ts, idss, base, outs, col = [], [], [], [], 0
+    for k, (V, D, bag) in enumerate(tables):
+        t = rnd(V, D, seed=60 + k).requires_grad_(True)
+        ids = torch.randint(0, V, (rows, bag), device=DEV)
+        ids.view(-1)[::97] = 0  # padding row
+        emb = F.embedding(ids, t, padding_idx=0)
+        outs.append(emb.sum(1))
+        base.append(dict(kind=_hip.RS_SEG_SPARSE if bag == 1 else _hip.RS_SEG_POOL, dim=D, out_col=col, vocab=V,
+                         idx_stride=bag, idx=ids.data_ptr(), table=t.data_ptr(), pad_idx=0,
+                         pool_mode=_hip.RS_POOL['sum'], bag=bag))
+        ts.append(t)
+        idss.append(ids)
+        col += D
+    assert col == dcol
+    torch.cat(outs, 1).backward(dout[:, :dcol])
+    gd = dout[:, dcol:dcol + 8].double()
+    ref_w, ref_b = (gd * x.double()).sum(0), gd.sum(0)
+    depth = rows // 32 + 32
+    tol_w = (depth + 1) * 2.0 ** -24 * (gd * x.double()).abs().sum(0)
+    tol_b = depth * 2.0 ** -24 * gd.abs().sum(0)
+
+    def run(det):
+        torch.use_deterministic_algorithms(det, warn_only=True)
+        try:
+            ops.sync_deterministic()
+            grads = [torch.full_like(t, 0.25) for t in ts]
+            gw, gb = torch.zeros(8, device=DEV), torch.zeros(8, device=DEV)
+            segs = [_seg(**s, grad=g.data_ptr()) for s, g in zip(base, grads)]
+            segs.append(_seg(kind=_hip.RS_SEG_DENSE, dim=8, out_col=dcol, idx_stride=1, x=x.data_ptr(),
+                             table=w.data_ptr(), bias=b.data_ptr(), grad=gw.data_ptr(), grad_bias=gb.data_ptr()))
+            assert _bwd_routes(segs, rows, ldo) == want[det]
+            ops.gather_bwd(segs, rows, dout)
+            torch.cuda.synchronize()
+        finally:
+            torch.use_deterministic_algorithms(False)
+            ops.sync_deterministic()
+        for t, g in zip(ts, grads):
+            err = (g - 0.25 - t.grad).abs().max().item()
+            assert err <= 2e-5 * max(1.0, t.grad.abs().max().item()), (det, tuple(t.shape), err)
+            assert (g[0] == 0.25).all()
+        assert ((gw.double() - ref_w).abs() <= tol_w).all() and ((gb.double() - ref_b).abs() <= tol_b).all()
+        return grads + [gw, gb]
+
+    run(False)
+    first, second = run(True), run(True)
+    for k, (g1, g2) in enumerate(zip(first, second)):
+        assert k == 0 or torch.equal(g1, g2), k  # segment 0 is the float-atomic scatter
 
 
 @pytest.mark.parametrize('B,D,Lb,mode', [(300, 128, 50, 'mean'), (300, 128, 50, 'sum'), (257, 64, 17, 'mean'),
