@@ -595,6 +595,27 @@ int rs_fused_topk(const float* U, int64_t ldu, int B, const void* items, int ite
 int rs_rescore_rows(const float* U, int64_t ldu, int B, const float* items, int64_t ldi, int64_t N, int D,
                     const int32_t* cand, const float* cand_val, int C, int64_t ld_cand, float* out_val,
                     int64_t ld_out, void* stream);
+/* Full-catalog rank of one target per user, from the same score tiles (csrc/retrieve.hip; the
+ * integer behind Recall / NDCG / MRR at any k): with m(b, j) the score rs_fused_topk orders by
+ * (the dot product of user b and column j, -inf for a column of the user's history; inputs, item
+ * dtypes and history exactly as there) and t = target_col[b * tc_stride],
+ *   out_rank[b] = #{ j != t : m(b, j) > m(b, t)  or  (m(b, j) == m(b, t) and j < t) },
+ * the 0-based position of column t in rs_fused_topk's order, so out_rank[b] < K exactly when t is
+ * among the user's top K, for every K (no K limit). The target is masked like any other column:
+ * one inside the user's own history ranks behind every column outside it. t outside [0, N):
+ * out_rank[b] = -1. The target's score comes from the same MFMA sequence as every other, so a
+ * column that holds a copy of the target's row ties with it. The column range is cut into
+ * `splits` parts (<= 0: rs_target_rank_splits; at most N) whose int32 partial counts go to ws
+ * (rs_target_rank_ws_bytes; unused with one split) and are added inside the call: the result does
+ * not depend on `splits`. N < 2^31, D a multiple of 16 in [16, 256], rows of U and items 16-byte
+ * aligned. */
+int rs_target_rank_splits(int B, int64_t N, int D);                       /* host only: the automatic choice, >= 1 */
+int64_t rs_target_rank_ws_bytes(int B, int64_t N, int D, int splits);     /* host only; splits <= 0: automatic */
+int rs_target_rank(const float* U, int64_t ldu, int B, const void* items, int items_bf16, int64_t ldi,
+                   int64_t N, int D, const int32_t* target_col, int64_t tc_stride,
+                   const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
+                   const int32_t* hist_idx, int64_t num_users, int splits, void* ws, int64_t ws_bytes,
+                   int32_t* out_rank, void* stream);
 
 /* ---------------------------------------------------------------- clip + Adam
  * Flat multi-tensor path over a contiguous fp32 range (all parameters packed in one buffer).

@@ -156,6 +156,10 @@ SIGNATURES = {
     'rs_fused_topk': (i32, [vp, i64, i32, vp, i32, i64, i64, i32, i32, vp, i64, vp, vp, i64, i32, vp, i64, vp,
                             vp, i64, vp]),
     'rs_rescore_rows': (i32, [vp, i64, i32, vp, i64, i64, i32, vp, vp, i32, i64, vp, i64, vp]),
+    'rs_target_rank_splits': (i32, [i32, i64, i32]),
+    'rs_target_rank_ws_bytes': (i64, [i32, i64, i32, i32]),
+    'rs_target_rank': (i32, [vp, i64, i32, vp, i32, i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, i32, vp, i64, vp,
+                             vp]),
     'rs_collate_ragged': (i32, [vp, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
     'rs_catalog_gather': (i32, [vp, i32, i32, i64, i32, i64, vp, i32, i32, i64, vp, i64, vp, vp]),
     'rs_sqnorm_ws_bytes': (i64, [i64]),

@@ -2,6 +2,8 @@
 // catalog columns of every user by dot product, with their scores, without the [B, N] score matrix
 // of the staged pipeline (rs_gemm_f32 -> rs_mask_history -> rs_topk_rows per column chunk,
 // retrieval.hip). Same result: value descending, ties by the lower column, history columns -inf.
+// Beside it, on the same tiles (retrieve_tile.h): the full-catalog rank of one target column per
+// user in that order (target_rank_kernel below; evaluation).
 //
 // Grid: row tiles x column splits, the row tiles of one split adjacent in dispatch order so that
 // their item reads meet in L2. A wave owns 32 users as the B operands of 32 x 32 MFMA tiles
@@ -21,10 +23,7 @@
 // them (ties by candidate position = column order). K <= 32: 4 waves x 32 users per workgroup,
 // lists of 80; K <= 256: one wave of 32 users, lists of 352 (rows x capacity x 8 B beside the item
 // tiles in 160 KiB).
-#include <type_traits>
-
-#include "common.h"
-#include "mfma.h"
+#include "retrieve_tile.h"
 
 namespace rs {
 namespace {
@@ -40,27 +39,6 @@ __device__ __forceinline__ float ft_key_value(uint32_t k) {
   const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
   return __uint_as_float(u);
 }
-
-// DP: the embedding width the registers and LDS are sized for (D <= DP); KB: the K bucket
-template <int DP, bool F32, int KB>
-struct FtCfg {
-  static constexpr int NW = KB == 0 ? 4 : 1;        // waves per workgroup
-  static constexpr int NT = 64 * NW;
-  static constexpr int ROWS = 32 * NW;              // users per workgroup
-  static constexpr int CAP = KB == 0 ? 80 : 352;    // list capacity: K + 32 <= CAP - 16
-  static constexpr int ESZ = F32 ? 4 : 2;
-  static constexpr int PTMAX = F32 ? DP + 4 : DP + 8;  // LDS row pitch (elements) at D = DP
-  // items per tile: two LDS buffers within 72 KB (one wave stages at most 64 rows)
-  static constexpr int TI = (KB == 0 && 2 * 128 * PTMAX * ESZ <= 72 * 1024) ? 128
-                            : (2 * 64 * PTMAX * ESZ <= 72 * 1024) ? 64 : 32;
-  static constexpr int NB = TI / 32;                // 32-item blocks per tile
-  static constexpr int CPR = DP * ESZ / 16;         // 16-byte chunks per item row at D = DP
-  static constexpr int SL = TI * CPR / NT;          // staged chunks per thread and tile
-  // tiles in flight in registers beyond the one in LDS (up to 64 staging VGPRs): with one, a
-  // workgroup per CU kept 16-32 KB in flight and the kernel ran at the load latency
-  static constexpr int DEPTH = SL <= 8 ? 2 : 1;
-  static_assert(TI * CPR % NT == 0, "whole chunks per thread");
-};
 
 struct FtArgs {
   const float* U;
@@ -119,8 +97,8 @@ template <int DP, bool F32, int KB>
 __global__ __launch_bounds__((FtCfg<DP, F32, KB>::NT)) void fused_topk_kernel(FtArgs a) {
   using Cfg = FtCfg<DP, F32, KB>;
   using E = std::conditional_t<F32, float, __bf16>;
-  constexpr int NT = Cfg::NT, ROWS = Cfg::ROWS, CAP = Cfg::CAP, TI = Cfg::TI, NB = Cfg::NB;
-  constexpr int CPR = Cfg::CPR, SL = Cfg::SL, ESZ = Cfg::ESZ;
+  constexpr int ROWS = Cfg::ROWS, CAP = Cfg::CAP, TI = Cfg::TI, NB = Cfg::NB;
+  constexpr int SL = Cfg::SL, ESZ = Cfg::ESZ;
   __shared__ __attribute__((aligned(16))) E tiles[2][TI * Cfg::PTMAX];
   __shared__ unsigned long long lists[ROWS * CAP];
   __shared__ int s_cnt[ROWS];
@@ -155,55 +133,17 @@ __global__ __launch_bounds__((FtCfg<DP, F32, KB>::NT)) void fused_topk_kernel(Ft
     }
   }
 
-  // user fragments (B operand). bf16: lane (c, h) holds U[o][16 s + 8 h .. + 7] of k-step s;
-  // fp32: U[o][h D/2 + s] (k-step s pairs embedding columns s and D/2 + s)
-  bf16x8 ub[F32 ? 1 : DP / 16];
-  float uf[F32 ? DP / 2 : 1];
-  if constexpr (F32) {
-#pragma unroll
-    for (int s4 = 0; s4 < DP / 8; ++s4) {
-      floatx4 x = {0.f, 0.f, 0.f, 0.f};
-      if (o_ok && 8 * s4 < D) x = ld4(a.U + (int64_t)o * a.ldu + h * (D / 2) + 4 * s4);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) uf[4 * s4 + j] = x[j];
-    }
-  } else {
-#pragma unroll
-    for (int s = 0; s < DP / 16; ++s) {
-      floatx4 x0 = {0.f, 0.f, 0.f, 0.f}, x1 = x0;
-      if (o_ok && 16 * s < D) {
-        const float* p = a.U + (int64_t)o * a.ldu + 16 * s + 8 * h;
-        x0 = ld4(p);
-        x1 = ld4(p + 4);
-      }
-      ub[s] = cvt8(x0, x1);
-    }
-  }
+  FtUser<DP, F32> uf;  // user fragments (B operand)
+  uf.load(a.U, a.ldu, o, o_ok, D, h);
 
-  // staging: chunk `slot` = 16 bytes `ch` of tile row `row` (the mapping of D = DP; a chunk past
-  // the row's end repeats its last one: same bytes to the same LDS address). Loads are
-  // unconditional, rows clamped to N - 1 (columns past c_end are masked where consumed).
+  // staging registers of the tiles in flight (retrieve_tile.h)
   constexpr int DEPTH = Cfg::DEPTH;
   u32x4 st[DEPTH][SL];
   const int cpr = D * ESZ / 16;
   auto load_tile = [&](u32x4 (&r)[SL], int t) {
-    const int64_t c0 = (int64_t)c_begin + (int64_t)t * TI;
-#pragma unroll
-    for (int i = 0; i < SL; ++i) {
-      const int slot = tid + NT * i;
-      const int row = slot / CPR, ch = min(slot % CPR, cpr - 1);
-      const int64_t g = min(c0 + row, (int64_t)a.N - 1);
-      r[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(a.items) + g * a.ldi * ESZ + ch * 16);
-    }
+    ft_load_tile<Cfg>(r, a.items, a.ldi, a.N, (int64_t)c_begin + (int64_t)t * TI, tid, cpr);
   };
-  auto store_tile = [&](const u32x4 (&r)[SL], int buf) {
-#pragma unroll
-    for (int i = 0; i < SL; ++i) {
-      const int slot = tid + NT * i;
-      const int row = slot / CPR, ch = min(slot % CPR, cpr - 1);
-      *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(tiles[buf]) + row * PT * ESZ + ch * 16) = r[i];
-    }
-  };
+  auto store_tile = [&](const u32x4 (&r)[SL], int buf) { ft_store_tile<Cfg>(r, tiles[buf], PT, tid, cpr); };
 
   // one 32-item block's scores: element e = column colbase + 8 (e >> 2) + 4 h + (e & 3), user c
   auto admit_block = [&](const floatx16& acc, int colbase) {
@@ -241,38 +181,8 @@ __global__ __launch_bounds__((FtCfg<DP, F32, KB>::NT)) void fused_topk_kernel(Ft
   };
 
   auto compute_tile = [&](int t) {
-    const E* T = tiles[t & 1];
     floatx16 acc[NB];
-#pragma unroll
-    for (int ib = 0; ib < NB; ++ib)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[ib][e] = 0.f;
-    if constexpr (F32) {
-#pragma unroll
-      for (int s4 = 0; s4 < DP / 8; ++s4) {
-        if (8 * s4 < D) {
-#pragma unroll
-          for (int ib = 0; ib < NB; ++ib) {
-            const floatx4 a4 = ld4(reinterpret_cast<const float*>(T) + (ib * 32 + c) * PT + h * (D / 2) + 4 * s4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-              acc[ib] = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[j], uf[4 * s4 + j], acc[ib], 0, 0, 0);
-          }
-        }
-      }
-    } else {
-#pragma unroll
-      for (int s = 0; s < DP / 16; ++s) {
-        if (16 * s < D) {
-#pragma unroll
-          for (int ib = 0; ib < NB; ++ib) {
-            const bf16x8 af = *reinterpret_cast<const bf16x8*>(reinterpret_cast<const __bf16*>(T) +
-                                                               (ib * 32 + c) * PT + 16 * s + 8 * h);
-            acc[ib] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af, ub[s], acc[ib], 0, 0, 0);
-          }
-        }
-      }
-    }
+    ft_mfma<DP, F32, NB>(tiles[t & 1], PT, D, c, h, uf, acc);
 #pragma unroll
     for (int ib = 0; ib < NB; ++ib) {
       float m = acc[ib][0];
@@ -318,6 +228,222 @@ __global__ __launch_bounds__((FtCfg<DP, F32, KB>::NT)) void fused_topk_kernel(Ft
   }
 }
 
+// Target rank (rs_target_rank): for every user the number of catalog columns that precede its
+// target column in rs_fused_topk's order (masked value descending, ties by the lower column); a
+// full-catalog rank without candidate lists, prunes or a K. Same grid, staging and MFMA tiles as
+// the four-wave fused_topk_kernel; only the two item tiles live in LDS.
+//
+// The target's score is formed by the same MFMA sequence as every other score, so that exact
+// copies of the target row tie with it: before the sweep a wave stages the target rows of its 32
+// users as one 32-item block (in the item tiles' LDS, not yet in use) and lane (c, h) takes the
+// diagonal element, item row c against user c. A target inside the user's own history scores -inf.
+//
+// Counting: a lane holds 16 scores of one user per block. A block that lies inside the split, holds
+// no lane's target and no history column of the wave's users is counted from the sign of s - thr
+// (s >= ts left of the target, s > ts right of it, as s >= the next float above ts). The
+// others take the exact test per element; history columns come from a per-lane cursor into the
+// user's sorted slice that only moves forward, like the columns, and count only when the target
+// itself is masked and they lie left of it. The count is a register; the two half-lanes of a user
+// add by one shuffle. One split writes the rank itself (one launch); otherwise each split stores
+// its partial count to ws [splits][B] and target_rank_reduce adds them: integer sums, the same
+// for every split count (int32 atomics would need the output zeroed first: a launch more for one
+// split, none fewer otherwise).
+constexpr int kTrNoCol = 0x7fffffff;  // past every column (N < 2^31): a cursor at its slice's end
+
+struct TrArgs {
+  const float* U;
+  int64_t ldu;
+  int B;
+  const void* items;
+  int64_t ldi;
+  int N, D;
+  const int32_t* target_col;
+  int64_t tc_stride;
+  const int64_t* user_ids;
+  int64_t uid_stride;
+  const int64_t* hist_off;
+  const int32_t* hist_idx;
+  int64_t num_users;
+  int splits, split_cols, nrt;
+  int32_t* out;  // one split: the ranks [B]; else this split's partial counts at split * B
+};
+
+template <int DP, bool F32>
+__global__ __launch_bounds__((FtCfg<DP, F32, 0>::NT)) void target_rank_kernel(TrArgs a) {
+  using Cfg = FtCfg<DP, F32, 0>;
+  using E = std::conditional_t<F32, float, __bf16>;
+  constexpr int NW = Cfg::NW, ROWS = Cfg::ROWS, TI = Cfg::TI, NB = Cfg::NB, SL = Cfg::SL, ESZ = Cfg::ESZ;
+  __shared__ __attribute__((aligned(16))) E tiles[2][TI * Cfg::PTMAX];
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int c = lane & 31, h = lane >> 5;
+  const int rt = blockIdx.x % a.nrt, split = blockIdx.x / a.nrt;
+  const int D = a.D;
+  const int PT = F32 ? D + 4 : D + 8;
+  const int o = rt * ROWS + wave * 32 + c;  // this lane's user
+  const bool o_ok = o < a.B;
+  const int c_begin = split * a.split_cols;
+  const int c_end = split == a.splits - 1 ? a.N : c_begin + a.split_cols;
+  const int ntiles = (c_end - c_begin + TI - 1) / TI;
+
+  int tcol = -1;  // the target column, -1: not in the catalog (or a row past B)
+  if (o_ok) {
+    const int t = a.target_col[(int64_t)o * a.tc_stride];
+    if (t >= 0 && t < a.N) tcol = t;
+  }
+  int64_t h_lo = 0, h_hi = 0;  // the user's CSR slice (sorted ascending)
+  if (o_ok && a.user_ids && a.hist_off && a.hist_idx) {
+    const int64_t uid = a.user_ids[(int64_t)o * a.uid_stride];
+    if (uid >= 0 && uid < a.num_users) {
+      h_lo = a.hist_off[uid];
+      h_hi = a.hist_off[uid + 1];
+    }
+  }
+
+  FtUser<DP, F32> uf;  // user fragments (B operand)
+  uf.load(a.U, a.ldu, o, o_ok, D, h);
+
+  constexpr int DEPTH = Cfg::DEPTH;
+  u32x4 st[DEPTH][SL];
+  const int cpr = D * ESZ / 16;
+  auto load_tile = [&](u32x4 (&r)[SL], int t) {
+    ft_load_tile<Cfg>(r, a.items, a.ldi, a.N, (int64_t)c_begin + (int64_t)t * TI, tid, cpr);
+  };
+  auto store_tile = [&](const u32x4 (&r)[SL], int buf) { ft_store_tile<Cfg>(r, tiles[buf], PT, tid, cpr); };
+  load_tile(st[0], 0);  // in flight during the target pass
+
+  // the target's score: WPR waves at a time stage their 32 target rows (a lane without a target
+  // reads row 0 and drops the result) into the 2 * TI rows of the item tiles
+  float ts = 0.f;
+  {
+    constexpr int WPR = 2 * TI / 32 < NW ? 2 * TI / 32 : NW;
+    E* blk = &tiles[0][0] + (wave % WPR) * 32 * PT;
+    for (int w0 = 0; w0 < NW; w0 += WPR) {
+      const bool mine = wave >= w0 && wave < w0 + WPR;
+      if (mine) {
+        for (int slot = lane; slot < 32 * cpr; slot += 64) {  // 32 cpr is a multiple of 64
+          const int row = slot / cpr, ch = slot % cpr;
+          const int64_t g = __shfl(max(tcol, 0), row);
+          *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(blk) + row * PT * ESZ + ch * 16) =
+              *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(a.items) + g * a.ldi * ESZ + ch * 16);
+        }
+      }
+      __syncthreads();
+      if (mine) {
+        floatx16 acc[1];
+        ft_mfma<DP, F32, 1>(blk, PT, D, c, h, uf, acc);
+        // item row c of the block is element 4 (c >> 3) + (c & 3) of the half-lane (c >> 2) & 1
+        const int ed = 4 * (c >> 3) + (c & 3);
+        float v = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) v = e == ed ? acc[0][e] : v;
+        const float w = __shfl_xor(v, 32);
+        ts = h == ((c >> 2) & 1) ? v : w;
+      }
+      __syncthreads();
+    }
+  }
+
+  // the history cursor: the first slice entry at or after the split's first column
+  int64_t hp = h_hi;
+  if (h_lo < h_hi) {
+    int64_t lo = h_lo, hi = h_hi;
+    while (lo < hi) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (a.hist_idx[mid] < c_begin) lo = mid + 1; else hi = mid;
+    }
+    hp = lo;
+    if (tcol >= 0) {  // the target is masked like any other column
+      lo = h_lo, hi = h_hi;
+      while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.hist_idx[mid] < tcol) lo = mid + 1; else hi = mid;
+      }
+      if (lo < h_hi && a.hist_idx[lo] == tcol) ts = -INFINITY;
+    }
+  }
+  int hnext = hp < h_hi ? a.hist_idx[hp] : kTrNoCol;
+  // s > ts  <=>  s >= ts_up, the next float above ts (ts = +-0: the smallest subnormal)
+  const uint32_t tb = __float_as_uint(ts);
+  const float ts_up = __uint_as_float(ts == 0.f ? 1u : (tb & 0x80000000u) ? tb - 1 : tb + 1);
+  int cnt = 0;
+
+  // one 32-item block's scores: element e = column colbase + 8 (e >> 2) + 4 h + (e & 3), user c
+  auto count_block = [&](const floatx16& acc, int colbase) {
+    if (colbase >= c_end) return;
+    const bool t_in = (unsigned)(tcol - colbase) < 32u;
+    const bool h_in = hnext - colbase < 32;
+    if (colbase <= c_end - 32 && !__any(t_in || h_in)) {
+      // s >= thr <=> the sign of s - thr is clear (f32 subnormals are kept, so the difference of
+      // unequal floats is never zero; x - x = +0): the 16 sign bits go through one funnel shift
+      // each into w, two VALU operations per score and no compare
+      const float thr = colbase < tcol ? ts : ts_up;
+      uint32_t w = 0;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) w = __builtin_amdgcn_alignbit(w, __float_as_uint(acc[e] - thr), 31);
+      cnt += 16 - __popc(w);
+      return;
+    }
+    uint32_t hmask = 0;  // bit e: element e is a history column of this user
+    while (hnext - colbase < 32) {
+      const int d = hnext - colbase;  // >= 0: the cursor never lags a block
+      if (((d >> 2) & 1) == h) hmask |= 1u << (4 * (d >> 3) + (d & 3));
+      ++hp;
+      hnext = hp < h_hi ? a.hist_idx[hp] : kTrNoCol;
+    }
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int col = colbase + 8 * (e >> 2) + 4 * h + (e & 3);
+      const float s = acc[e];
+      const bool left = col < tcol;
+      const bool live = (unsigned)col < (unsigned)c_end && col != tcol;
+      const bool raw = s > ts || (s == ts && left);
+      const bool hist = (hmask >> e) & 1u;
+      cnt += live && (hist ? (ts == -INFINITY && left) : raw) ? 1 : 0;
+    }
+  };
+
+  auto compute_tile = [&](int t) {
+    floatx16 acc[NB];
+    ft_mfma<DP, F32, NB>(tiles[t & 1], PT, D, c, h, uf, acc);
+#pragma unroll
+    for (int ib = 0; ib < NB; ++ib) count_block(acc[ib], c_begin + t * TI + ib * 32);
+  };
+
+  // the tile pipeline of fused_topk_kernel
+  store_tile(st[0], 0);
+#pragma unroll
+  for (int d = 0; d < DEPTH; ++d) load_tile(st[d], 1 + d);
+  __syncthreads();
+  for (int t0 = 0; t0 < ntiles; t0 += DEPTH) {
+#pragma unroll
+    for (int d = 0; d < DEPTH; ++d) {
+      const int t = t0 + d;
+      if (t < ntiles) {
+        compute_tile(t);
+        store_tile(st[d], (t + 1) & 1);
+        load_tile(st[d], t + 1 + DEPTH);
+        __syncthreads();
+      }
+    }
+  }
+
+  cnt += __shfl_xor(cnt, 32);
+  if (h == 0 && o_ok) a.out[(int64_t)split * a.B + o] = a.splits == 1 && tcol < 0 ? -1 : cnt;
+}
+
+// out[b] = the sum of the splits' partial counts, -1 for a target outside the catalog
+__global__ __launch_bounds__(256) void target_rank_reduce(const int32_t* __restrict__ part, int splits, int B,
+                                                          const int32_t* __restrict__ target_col,
+                                                          int64_t tc_stride, int N, int32_t* __restrict__ out) {
+  const int b = blockIdx.x * 256 + threadIdx.x;
+  if (b >= B) return;
+  const int t = target_col[(int64_t)b * tc_stride];
+  int r = 0;
+  for (int s = 0; s < splits; ++s) r += part[(int64_t)s * B + b];
+  out[b] = t >= 0 && t < N ? r : -1;
+}
+
 // one wave per candidate: out[b, j] = U[b] . items[cand[b, j]]
 __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ U, int64_t ldu, int B,
                                                       const float* __restrict__ items, int64_t ldi, int64_t N,
@@ -360,6 +486,18 @@ int ft_launch(const FtArgs& a, int grid, hipStream_t st) {
   if (a.D <= 64) return ft_launch_k<64, F32>(a, grid, st);
   if (a.D <= 128) return ft_launch_k<128, F32>(a, grid, st);
   return ft_launch_k<256, F32>(a, grid, st);
+}
+
+template <bool F32>
+int tr_launch(const TrArgs& a, int grid, hipStream_t st) {
+  if (a.D <= 64)
+    target_rank_kernel<64, F32><<<grid, FtCfg<64, F32, 0>::NT, 0, st>>>(a);
+  else if (a.D <= 128)
+    target_rank_kernel<128, F32><<<grid, FtCfg<128, F32, 0>::NT, 0, st>>>(a);
+  else
+    target_rank_kernel<256, F32><<<grid, FtCfg<256, F32, 0>::NT, 0, st>>>(a);
+  RS_CHECK_LAUNCH("rs_target_rank");
+  return 0;
 }
 
 }  // namespace
@@ -428,6 +566,64 @@ extern "C" int rs_fused_topk(const float* U, int64_t ldu, int B, const void* ite
   if (splits == 1) return 0;
   // split-major candidates, sorted within a split: position order == column order among equal values
   return rs_topk_rows(ws_val, ldw, B, (int)ldw, K, ws_idx, ldw, 0, out_idx, out_val, ld_out, stream);
+}
+
+extern "C" int rs_target_rank_splits(int B, int64_t N, int D) {
+  (void)D;
+  if (B < 1 || N < 1) return 1;
+  // one round of workgroups over the 256 CUs, as rs_fused_topk_splits; no lists to warm up, so
+  // the only floor is 2048 columns a split (its tile pipeline's fill against its sweep)
+  const int64_t want = cdiv(256, cdiv(B, 128));
+  const int64_t most = N / 2048;
+  int64_t s = want < most ? want : most;
+  if (s > 1024) s = 1024;
+  return s < 1 ? 1 : (int)s;
+}
+
+extern "C" int64_t rs_target_rank_ws_bytes(int B, int64_t N, int D, int splits) {
+  if (splits <= 0) splits = rs_target_rank_splits(B, N, D);
+  if (B < 1 || splits == 1) return 16;
+  const int64_t n = (int64_t)B * splits * 4;  // int32 partial counts [splits][B]
+  return n < 16 ? 16 : n;
+}
+
+extern "C" int rs_target_rank(const float* U, int64_t ldu, int B, const void* items, int items_bf16,
+                              int64_t ldi, int64_t N, int D, const int32_t* target_col, int64_t tc_stride,
+                              const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
+                              const int32_t* hist_idx, int64_t num_users, int splits, void* ws,
+                              int64_t ws_bytes, int32_t* out_rank, void* stream) {
+  RS_CHECK_ARG(U && items && target_col && out_rank && B >= 0,
+               "rs_target_rank: null U / items / target_col / out_rank or B < 0");
+  RS_CHECK_ARG(D >= 16 && D <= 256 && D % 16 == 0,
+               "rs_target_rank: D = %d, must be a multiple of 16 in [16, 256]", D);
+  RS_CHECK_ARG(N >= 1 && N < (int64_t)1 << 31, "rs_target_rank: bad sizes (N=%lld; 1 <= N < 2^31)", (long long)N);
+  RS_CHECK_ARG(ldu >= D && ldu % 4 == 0 && ldi >= D && ldi % (items_bf16 ? 8 : 4) == 0 && aligned16(U) &&
+                   aligned16(items),
+               "rs_target_rank: rows of U and items must be 16-byte aligned, ld >= D");
+  if (splits <= 0) splits = rs_target_rank_splits(B, N, D);
+  RS_CHECK_ARG(splits <= N, "rs_target_rank: splits = %d leaves a split no column (N=%lld)", splits, (long long)N);
+  const int64_t need = splits > 1 ? rs_target_rank_ws_bytes(B, N, D, splits) : 0;
+  RS_CHECK_ARG(splits == 1 || (ws && ws_bytes >= need),
+               "rs_target_rank: workspace of %lld bytes, needs %lld (rs_target_rank_ws_bytes)",
+               (long long)ws_bytes, (long long)need);
+  if (B == 0) return 0;
+  TrArgs a;
+  a.U = U; a.ldu = ldu; a.B = B;
+  a.items = items; a.ldi = ldi; a.N = (int)N; a.D = D;
+  a.target_col = target_col; a.tc_stride = tc_stride;
+  a.user_ids = user_ids; a.uid_stride = uid_stride; a.hist_off = hist_off; a.hist_idx = hist_idx;
+  a.num_users = num_users;
+  a.splits = splits; a.split_cols = (int)(N / splits); a.nrt = cdiv(B, 128);
+  a.out = splits == 1 ? out_rank : static_cast<int32_t*>(ws);
+  const int64_t grid = (int64_t)a.nrt * splits;
+  RS_CHECK_ARG(grid < (int64_t)1 << 31, "rs_target_rank: grid too large");
+  RS_RET_IF(items_bf16 ? tr_launch<false>(a, (int)grid, as_stream(stream))
+                       : tr_launch<true>(a, (int)grid, as_stream(stream)));
+  if (splits == 1) return 0;
+  target_rank_reduce<<<cdiv(B, 256), 256, 0, as_stream(stream)>>>(a.out, splits, B, target_col, tc_stride, (int)N,
+                                                                 out_rank);
+  RS_CHECK_LAUNCH("rs_target_rank (reduce)");
+  return 0;
 }
 
 extern "C" int rs_rescore_rows(const float* U, int64_t ldu, int B, const float* items, int64_t ldi, int64_t N,

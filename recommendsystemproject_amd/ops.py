@@ -630,6 +630,49 @@ def fused_topk(U, items, K, user_ids=None, history=None, splits=0):
     return idx, val
 
 
+def target_rank(U, items, target_cols, user_ids=None, history=None, splits=0):
+    """For every user the 0-based position of catalog column target_cols[b] in fused_topk's order
+    over the whole catalog (rs_target_rank): the number of columns with a higher masked score, or
+    an equal one and a lower column. rank < K exactly when the target is among the user's top K,
+    for any K. U, items, user_ids and history as fused_topk's (history applies to the target too);
+    target_cols integer [B], a column outside [0, N) ranks -1. -> int32 [B]. No CPU fallback."""
+    use_hist = history is not None and user_ids is not None
+    for t in (U, items, target_cols) + ((user_ids,) + tuple(history[:2]) if use_hist else ()):
+        _hip.require_device(t)
+    if items.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'target_rank: items must be float32 or bfloat16, got {items.dtype}')
+    U = U.float()
+    if U.stride(1) != 1 or U.stride(0) % 4 or U.data_ptr() % 16:
+        U = U.contiguous()
+    if items.stride(1) != 1 or (items.stride(0) * items.element_size()) % 16 or items.data_ptr() % 16:
+        items = items.contiguous()
+    B, D = int(U.shape[0]), int(U.shape[1])
+    N = int(items.shape[0])
+    tc = target_cols.reshape(-1)
+    if tc.numel() != B:
+        raise ValueError(f'target_rank: {tc.numel()} target columns for {B} users')
+    if tc.dtype != torch.int32:
+        # an id beyond int32 is no column of a catalog with N < 2^31: keep it out of range
+        tc = tc.long().clamp(-1, N).int()
+    L = _hip.lib()
+    if splits <= 0:
+        splits = L.rs_target_rank_splits(B, N, D)
+    nbytes = L.rs_target_rank_ws_bytes(B, N, D, splits) if splits > 1 else 0
+    w = ws(nbytes, U.device) if splits > 1 else None
+    out = torch.empty(B, device=U.device, dtype=torch.int32)
+    if B == 0:
+        return out
+    uid, us, off, hidx, nu = None, 0, None, None, 0
+    if use_hist:
+        uid = user_ids if user_ids.dtype == torch.int64 else user_ids.long()
+        us = int(uid.stride(0))
+        off, hidx, nu = history
+    call('rs_target_rank', P(U), int(U.stride(0)), B, P(items), int(items.dtype == torch.bfloat16),
+         int(items.stride(0)), N, D, P(tc), int(tc.stride(0)), P(uid), us, P(off), P(hidx), int(nu),
+         int(splits), P(w), int(nbytes), P(out), stream())
+    return out
+
+
 def rescore_rows(U, items, cand, cand_val=None):
     """out[b, j] = fp32 dot of U[b] with items[cand[b, j]] (rs_rescore_rows); -inf where cand_val is
     -inf. U, items fp32 [., D]; cand int32 [B, C]."""

@@ -167,20 +167,31 @@ class TwoTowerModel(nn.Module):
     def get_item_embeddings(self, item_inputs):
         return self.item_tower(item_inputs, self.item_feature_mapping)
 
-    def recommend(self, user_inputs, index, k, user_ids=None, oversample=1):
-        """The k best items of `index` (retrieval.ItemIndex) for each user of `user_inputs` (a
-        user-tower batch): the user tower alone in eval mode under no_grad, then index.search.
-        -> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first."""
+    def _serving_user_emb(self, user_inputs):
+        """The user tower alone in eval mode under no_grad; the previous mode is restored."""
         _hip.require_device(self.user_tower.feature_bn.weight)
         ensure_flat(self)
         was_training = self.training
         self.eval()
         try:
             with torch.no_grad():
-                user_emb = self.user_tower(user_inputs, self.user_feature_mapping)
+                return self.user_tower(user_inputs, self.user_feature_mapping)
         finally:
             self.train(was_training)
+
+    def recommend(self, user_inputs, index, k, user_ids=None, oversample=1):
+        """The k best items of `index` (retrieval.ItemIndex) for each user of `user_inputs` (a
+        user-tower batch): the user tower alone in eval mode under no_grad, then index.search.
+        -> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first."""
+        user_emb = self._serving_user_emb(user_inputs)
         return index.search(user_emb, k, user_ids=user_ids, oversample=oversample)
+
+    def rank_targets(self, user_inputs, index, target_item_ids, user_ids=None):
+        """The full-catalog rank of each user's target item in `index` (retrieval.ItemIndex.rank):
+        the user tower alone in eval mode under no_grad, then index.rank. -> int32 [B], 0 = best,
+        -1 for an item the catalog does not hold."""
+        user_emb = self._serving_user_emb(user_inputs)
+        return index.rank(user_emb, target_item_ids, user_ids=user_ids)
 
     _NAN_MSG = {1: 'Found NaN in User Embedding', 2: 'Found NaN in Item Embedding',
                 4: 'Found NaN in Hard Negative Embedding'}

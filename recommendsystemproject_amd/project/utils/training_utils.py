@@ -287,6 +287,105 @@ def validate(model, loader, item_loader, device, epoch, k_list=[10, 20],
     return avg_loss, acc_dict
 
 
+# ============================================================================ full-catalog ranking metrics
+def _ranking_sums(ranks, k_list):
+    """The order-independent sums behind ranking_metrics, on ranks' device: int64 [hits@k ...,
+    rank sum, ranked, samples] and float64 [dcg@k ..., reciprocal-rank sum]."""
+    r = ranks.reshape(-1).long()
+    ok = r >= 0
+    rd = r.clamp(min=0).double()
+    zero = torch.zeros((), dtype=torch.float64, device=r.device)
+    gain = torch.where(ok, 1.0 / torch.log2(rd + 2.0), zero)
+    within = [ok & (r < int(k)) for k in k_list]
+    counts = torch.stack([w.sum() for w in within] +
+                         [torch.where(ok, r + 1, torch.zeros_like(r)).sum(), ok.sum(),
+                          torch.tensor(r.numel(), dtype=torch.int64, device=r.device)])
+    sums = torch.stack([torch.where(w, gain, zero).sum() for w in within] +
+                       [torch.where(ok, 1.0 / (rd + 1.0), zero).sum()])
+    return counts, sums
+
+
+def _ranking_finish(counts, sums, k_list):
+    counts, sums = counts.tolist(), sums.tolist()
+    nk = len(k_list)
+    rank_sum, ranked, n = counts[nk], counts[nk + 1], counts[nk + 2]
+    out = {}
+    for i, k in enumerate(k_list):
+        out[f'recall@{k}'] = counts[i] / max(n, 1)
+        out[f'ndcg@{k}'] = sums[i] / max(n, 1)
+    out['mrr'] = sums[nk] / max(n, 1)
+    out['mean_rank'] = rank_sum / ranked if ranked else float('nan')
+    out['num_ranked'] = int(ranked)
+    out['num_samples'] = int(n)
+    return out
+
+
+def ranking_metrics(ranks, k_list):
+    """Metrics of one relevant item per sample from its 0-based full-catalog rank r (ItemIndex.rank;
+    -1: the item is not in the catalog, a miss everywhere and left out of mean_rank). Pure torch on
+    ranks' device (CPU tensors too), any k, also beyond the catalog size:
+      recall@k = mean [0 <= r < k]              ndcg@k = mean [0 <= r < k] / log2(r + 2)  (ideal DCG 1)
+      mrr = mean 1 / (r + 1)                    mean_rank = mean of r + 1 over the ranked samples
+    (nan without one), with num_ranked and num_samples. Integer counts and float64 sums."""
+    k_list = list(k_list)
+    return _ranking_finish(*_ranking_sums(ranks, k_list), k_list)
+
+
+def _batch_target_ids(item_batch, item_id_feature, item_id_type, item_id_col_idx):
+    """validate()'s target extraction from a batch's item tower."""
+    if item_id_type == 'sparse' and 'sparse' in item_batch:
+        return item_batch['sparse'][:, item_id_col_idx]
+    if item_id_type == 'dense' and 'dense' in item_batch:
+        return item_batch['dense'][:, item_id_col_idx]
+    if item_id_type == 'sequence' and 'sequence' in item_batch:
+        return item_batch['sequence'][item_id_feature][:, 0]
+    raise ValueError(f"Cannot extract target item IDs from batch. item_batch keys: "
+                     f"{item_batch.keys()}, looking for type: {item_id_type}")
+
+
+def evaluate_ranking(model, loader, item_loader, device, k_list=(10, 20), item_id_feature='movie_id_enc',
+                     item_id_type='sparse', item_id_col_idx=0, meta_data_loader=None, user_id_col_idx=None,
+                     user_history=None, index_dtype='fp32'):
+    """Full-catalog ranking metrics of the held-out item of every validation sample: the item
+    index of validate() (ItemIndex.build, the user history excluded as there), each batch's target
+    ranks through the fused rank kernel (TwoTowerModel.rank_targets; no [B, N] scores, no limit
+    on k), accumulated on the device: the host reads the sums once, after the last batch. Loaders,
+    target extraction and the user-id sources are validate()'s. -> ranking_metrics' dict over all
+    samples; its recall@k is validate()'s Recall@k wherever validate can compute it (unique
+    catalog ids)."""
+    from recommendsystemproject_amd.retrieval import ItemIndex
+    k_list = list(k_list)
+    index = ItemIndex.build(model, item_loader, device, dtype=index_dtype, item_id_feature=item_id_feature,
+                            item_id_type=item_id_type, item_id_col=item_id_col_idx)
+    if user_history is not None:
+        index.set_history(user_history)
+    meta_iter = iter(meta_data_loader) if meta_data_loader is not None else None
+    counts = sums = None
+    for batch_data in tqdm(loader, desc="Ranking"):
+        batch_data = to_device(batch_data, device)
+        item_batch = batch_data.get('item_tower', {})
+        if not item_batch:
+            raise ValueError("batch_data does not contain 'item_tower' key")
+        targets = _batch_target_ids(item_batch, item_id_feature, item_id_type, item_id_col_idx)
+        user_ids = None
+        if user_history is not None:
+            if meta_iter is not None:
+                user_ids = next(meta_iter)['user_tower']['sparse'][:, 0].to(device)
+            elif user_id_col_idx is not None:
+                user_ids = batch_data.get('user_tower', {})['sparse'][:, user_id_col_idx]
+            else:
+                raise ValueError("Either metadata_loader or user_id_col_idx required")
+            user_ids = user_ids.long()
+        ranks = model.rank_targets(batch_data['user_tower'], index, targets, user_ids=user_ids)
+        c, s = _ranking_sums(ranks, k_list)
+        counts = c if counts is None else counts + c
+        sums = s if sums is None else sums + s
+    if counts is None:
+        return ranking_metrics(torch.zeros(0, dtype=torch.int32), k_list)
+    _check_errors(model)
+    return _ranking_finish(counts, sums, k_list)
+
+
 def _log_embedding_stats(all_item_embs, epoch):
     """Item-embedding diagnostics (training_utils.py:277-325; logging only)."""
     emb_std = all_item_embs.std(dim=0).mean().item()

@@ -9,6 +9,12 @@ ties by the lower catalog column, a user's history excluded).
     index = ItemIndex.build(model, item_loader, device, dtype='bf16')
     index.set_history(user_history)                       # optional: never recommend these again
     item_ids, scores, cols = model.recommend(batch['user_tower'], index, k=20, user_ids=uids)
+
+`rank(user_emb, target_item_ids)` answers the evaluation question instead: where in that same
+ordering over the WHOLE catalog does each user's held-out item stand (rs_target_rank, one integer
+per user; training_utils.ranking_metrics turns it into Recall / NDCG at any k, MRR, mean rank).
+
+    ranks = model.rank_targets(batch['user_tower'], index, target_item_ids, user_ids=uids)
 """
 from __future__ import annotations
 
@@ -63,6 +69,7 @@ class ItemIndex:
         self.item_ids = item_ids
         self._dtype = dtype
         self._history = None
+        self._by_id = None  # (sorted ids, their columns), built by the first columns_of
 
     @classmethod
     def from_embeddings(cls, embs, item_ids=None, dtype='fp32', keep_fp32=True):
@@ -149,6 +156,73 @@ class ItemIndex:
         else:
             cols, val = ops.fused_topk(U, rows, k, user_ids, hist)
         return self.item_ids[cols.long()], val, cols
+
+    def columns_of(self, item_ids):
+        """item ids -> their catalog columns, int32 of the same shape on the index's device; -1 for
+        an id that is not in the catalog. An id the catalog holds twice maps to its last column
+        (the reference's id_to_index_map assignment keeps the last writer)."""
+        if self._by_id is None:  # built once: the ids sorted (stable, so equal ids keep column order)
+            sorted_ids, order = torch.sort(self.item_ids, stable=True)
+            self._by_id = (sorted_ids.contiguous(), order.int())
+        sorted_ids, order = self._by_id
+        q = torch.as_tensor(item_ids).to(sorted_ids.device).long()
+        flat = q.reshape(-1).contiguous()
+        if sorted_ids.numel() == 0:
+            return torch.full_like(q, -1, dtype=torch.int32)
+        pos = (torch.searchsorted(sorted_ids, flat, right=True) - 1).clamp(min=0)  # the last equal id
+        cols = torch.where(sorted_ids[pos] == flat, order[pos], torch.full_like(order[pos], -1))
+        return cols.reshape(q.shape)
+
+    def rank(self, user_emb, target_item_ids, user_ids=None):
+        """-> int32 [B]: the 0-based position of each user's target item in the full ordering that
+        search() takes its first k from (value descending, ties by the lower column, the user's
+        history at -inf, the target's own membership included), so rank < k exactly when search(k)
+        returns the item; -1 for an item id the catalog does not hold. One pass of the fused rank
+        kernel (ops.target_rank) on the index's own rows, any catalog size, no score matrix: there
+        a column holding a copy of the target's row ties with it bit for bit. Embedding widths the
+        kernel does not take (fused_supported) go through the staged pieces chunk by chunk against
+        the gathered target score: the same definition, but the target's score is summed in another
+        order than the chunk's, so equal rows need not tie exactly."""
+        rows = self._rows()
+        _hip.require_device(user_emb)
+        _hip.require_device(rows)
+        hist = self._history if user_ids is not None else None
+        U = user_emb.detach().float().contiguous()
+        cols = self.columns_of(torch.as_tensor(target_item_ids).reshape(-1))
+        if cols.numel() != U.shape[0]:
+            raise ValueError(f'{cols.numel()} target items for {U.shape[0]} users')
+        if fused_supported(self.dim):
+            return ops.target_rank(U, rows, cols, user_ids, hist)
+        return self._rank_staged(U, cols, user_ids, hist)
+
+    def _rank_staged(self, U, cols, user_ids, hist, chunk=65536):
+        """Embedding widths the fused kernel does not take: per column chunk the GEMM scores and
+        the device history mask, compared against the gathered (and equally masked) target score."""
+        rows = self._fp32 if self._fp32 is not None else self._bf16.float()
+        B, D = int(U.shape[0]), int(U.shape[1])
+        N = len(self)
+        tcol = cols.long().view(-1, 1)
+        gather = cols.clamp(min=0).view(-1, 1).contiguous()
+        ts = ops.rescore_rows(U, rows, gather)
+        uid = None
+        if hist is not None:
+            uid = user_ids.long().reshape(-1).contiguous()
+            _hip.require_device(uid)
+            ts = self._mask_gathered(ts, gather, uid, hist, N)
+        count = torch.zeros(B, device=U.device, dtype=torch.int64)
+        S = torch.empty(B * min(chunk, N), device=U.device, dtype=torch.float32)
+        for c0 in range(0, N, chunk):
+            n = min(chunk, N - c0)
+            Sc = S[:B * n].view(B, n)
+            ops.gemm(U, rows[c0:c0 + n], Sc, B, n, D, transA=0, transB=1, lda=D, ldb=D, ldc=n)
+            if hist is not None:
+                off, idx, nu = hist
+                _hip.call('rs_mask_history', Sc.data_ptr(), n, B, c0, n, uid.data_ptr(), int(uid.stride(0)),
+                          off.data_ptr(), idx.data_ptr(), nu, ops.stream())
+            col = torch.arange(c0, c0 + n, device=U.device).view(1, -1)
+            ahead = (Sc > ts) | ((Sc == ts) & (col < tcol))
+            count += (ahead & (col != tcol)).sum(dim=1)
+        return torch.where(tcol.view(-1) >= 0, count, torch.full_like(count, -1)).int()
 
     def _search_staged(self, U, k, user_ids, hist):
         """Embedding widths the fused kernel does not take: the staged pipeline, scores gathered."""
