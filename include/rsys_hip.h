@@ -243,6 +243,36 @@ int rs_ffn_fwd_bf16(int M, int F, const float* x, const float* W1, const float* 
 int rs_ffn_bwd_bf16(int M, int F, const float* x, const float* W1, const float* b1, const float* W2,
                     const uint64_t* mask, const float* dff, const float* dres, float* dx, void* f1,
                     void* dpre, float p, void* stream);
+
+/* ---------------------------------------------------------------- chained forward tail (bf16 mode)
+ * A Linear computed from the rows the previous stage still holds on chip (csrc/chain.h), so the
+ * rows are not read back from HBM by a kernel of their own. Every output has the bits of the
+ * separate calls named below on the same inputs.
+ *
+ * rs_layer_tail_fwd_bf16: the encoder layer behind the attention, one pass over the rows:
+ *     h1 = resid + drop(att Wo^T + bo), x1 = LN1(h1)       = rs_gemm_add_layernorm[_rows] (site0)
+ *     x2 = LN2(x1 + drop(linear2(drop(relu(linear1(x1))))))  = rs_ffn_fwd_bf16 (site1, site2)
+ *     qkv = x2 Win^T + bin, bf16 [M,192]                    = rs_gemm_f32, RS_GEMM_C_BF16
+ *   att / resid / h1 / x1 / h2 / x2 [M,64], Wo [64,ldwo], Win [192,ldwin]. Win, bin and qkv may
+ *   all be null (no qkv). x1 may be null: it is not stored (see rs_ffn_wgrad_ln_bf16).
+ *   resid_rows non-null: row m's residual is resid row m * resid_bag + resid_rows[m].
+ *   M % 16 == 0, F == 256, M * F < 2^32.
+ * rs_ffn_wgrad_ln_bf16: rs_ffn_wgrad_bf16 for a forward that did not store x1:
+ *   x1 = (h1 - mean1) * rstd1 * gamma1 + beta1 is rebuilt while the rows are staged, with the
+ *   forward's operations, so the gradients have rs_ffn_wgrad_bf16's bits on the forward's x1.
+ *   ws: rs_ffn_wgrad_ws_bytes. */
+int rs_layer_tail_fwd_bf16(int M, int F, const float* att, const float* Wo, int ldwo, const float* bo,
+                           const float* resid, const int64_t* resid_rows, int resid_bag,
+                           const float* gamma1, const float* beta1, float eps1, float* h1, float* x1,
+                           float* mean1, float* rstd1, const float* W1, const float* b1, const float* W2,
+                           const float* b2, const float* gamma2, const float* beta2, float eps2, float* h2,
+                           float* x2, float* mean2, float* rstd2, uint64_t* mask, const float* Win,
+                           int ldwin, const float* bin, void* qkv, float p, const int64_t* key, int site0,
+                           int site1, int site2, void* stream);
+int rs_ffn_wgrad_ln_bf16(int M, int F, const float* h1, const float* mean1, const float* rstd1,
+                         const float* gamma1, const float* beta1, const float* W1, const float* b1,
+                         const float* W2, const uint64_t* mask, const float* dff, float p, float* dW1,
+                         float* db1, float* dW2, float* db2, float* ws, void* stream);
 /* rs_ffn_bwd_bf16 with the backward of the LayerNorm that produced x (norm1 of the same
  * TransformerEncoderLayer, x1 = LN1(h1)) fused into its epilogue: dx never reaches HBM; writes
  * dh1 = LN1-backward(dx) (h1, gamma1, mean1, rstd1 of the forward), dsa = dropout-backward of
@@ -260,7 +290,7 @@ int rs_ffn_bwd_ln_bf16(int M, int F, const float* x, const float* W1, const floa
  * mean2 / rstd2 / gamma2) instead of dff / dres; writes dff = drop2(dh2) [M, 64] (the operand of
  * rs_ffn_wgrad_bf16), dh1, dsa (p > 0; NULL: not stored, for rs_outproj_bwd_bf16, which masks dh1
  * itself) and accumulates dgamma1/dbeta1, dgamma2/dbeta2
- * (fixed-order partials in ws: rs_ffn_bwd_ln2_ws_bytes). Replaces rs_layernorm_bwd (norm2) +
+ * (fixed-order partials in ws: rs_ffn_bwd_ln2_ws_bytes). x is not read and may be null. Replaces rs_layernorm_bwd (norm2) +
  * rs_ffn_bwd_ln_bf16 of TransformerEncoderLayer's backward (SequenceEncoder.py:17-29; post-LN,
  * norm_first=False). Only dh1 may alias dy2. */
 int64_t rs_ffn_bwd_ln2_ws_bytes(int M, int F);

@@ -77,6 +77,9 @@ SIGNATURES = {
     'rs_ffn_mask_words': (i64, [i32, i32]),
     'rs_ffn_fwd_bf16': (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, f32, vp,
                               i32, i32, vp]),
+    'rs_layer_tail_fwd_bf16': (i32, [i32, i32, vp, vp, i32, vp, vp, vp, i32, vp, vp, f32, vp, vp, vp, vp, vp, vp,
+                                     vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp, i32, vp, vp, f32, vp, i32, i32,
+                                     i32, vp]),
     'rs_ffn_bwd_bf16': (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp]),
     'rs_ffn_bwd_ln_ws_bytes': (i64, [i32, i32]),
     'rs_ffn_bwd_ln_bf16': (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
@@ -87,6 +90,7 @@ SIGNATURES = {
     'rs_wgrad_ws_bytes': (i64, [i32, i32, i32]),
     'rs_ffn_wgrad_ws_bytes': (i64, [i32, i32]),
     'rs_ffn_wgrad_bf16': (i32, [i32, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]),
+    'rs_ffn_wgrad_ln_bf16': (i32, [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp, vp, vp, vp]),
     'rs_wgrad_bf16': (i32, [i32, i32, i32, vp, i32, i32, vp, i32, i32, f32, vp, i32, vp, vp, vp]),
     'rs_linear_bwd_bf16_ws_bytes': (i64, [i32, i32, i32]),
     'rs_linear_bwd_bf16': (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),

@@ -30,6 +30,7 @@
 #include "rng.h"
 #include "mfma.h"
 #include "stage.h"
+#include "chain.h"
 
 namespace rs {
 namespace {
@@ -67,6 +68,7 @@ struct FfnArgs {
   // dsa = dropout-backward(dh1) (site ln_site), and [grid][128] dgamma | dbeta partials
   const float* ln_h;
   const float* ln_gamma;
+  const float* ln_beta;  // rs_ffn_wgrad_ln_bf16 only (x1 rebuilt from ln_h)
   const float* ln_mean;
   const float* ln_rstd;
   float* ln_da;  // nullable (p == 0)
@@ -112,10 +114,123 @@ __device__ __forceinline__ void load_row64(const float* base, int64_t m, int q, 
     ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds8(bp_ + 8), (AF)[1], ACC, 0, 0, 0);    \
   } while (0)
 
+// The forward's two products for one 16-row group: f1 = drop(relu(af W1^T + b1)) stays in
+// registers as linear2's operand fragments; returns acc2 = f1 W2^T (no bias yet) and the row's
+// keep-and-positive bits. Shared by rs_ffn_fwd_bf16 and rs_layer_tail_fwd_bf16.
+template <int F, bool DROP>
+__device__ __forceinline__ void ffn_products(const bf16x8 (&af)[2], const __bf16* W1i, const __bf16* W2i,
+                                             const float* sb1, const DropKey& k1, uint32_t base1, int r,
+                                             int q, uint64_t& bits, floatx4 (&acc2)[4]) {
+  constexpr int FP = F + 8;
+  constexpr int NH = F / 16, NC = F / 32;
+  // linear1 + bias + relu + dropout, 4 tiles at a time, into linear2's operand fragments
+  bf16x8 a2[NC];
+  bits = 0;
+#pragma unroll
+  for (int h0 = 0; h0 < NH; h0 += 4) {
+    floatx4 acc[4];
+#pragma unroll
+    for (int hh = 0; hh < 4; ++hh) {
+      acc[hh] = floatx4{0.f, 0.f, 0.f, 0.f};
+      RS_MFMA2(acc[hh], W1i, DP, (h0 + hh) * 16 + r, af);
+    }
+#pragma unroll
+    for (int hh = 0; hh < 4; ++hh) {
+      const int h = h0 + hh, n0 = 16 * h + 4 * q;
+      const floatx4 bv = *reinterpret_cast<const floatx4*>(sb1 + n0);
+      float mk[4];
+      if constexpr (DROP) keep4_32(k1, base1 + 16 * h, mk);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        float v = acc[hh][i] * 1.0f + bv[i];
+        v = fmaxf(v, 0.f);
+        if constexpr (DROP) v *= mk[i];
+        if (v > 0.f) bits |= 1ull << (4 * h + i);
+        a2[h >> 1][4 * (h & 1) + i] = (__bf16)v;
+      }
+    }
+  }
+  // linear2 over the permuted k slices
+#pragma unroll
+  for (int t = 0; t < 4; ++t) acc2[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = 0; c < NC; ++c)
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds8(W2i + (16 * t + r) * FP + 32 * c + 8 * q),
+                                                         a2[c], acc2[t], 0, 0, 0);
+}
+
+// One element of LayerNorm's output from the stored statistics: the forward epilogue (add_ln64)
+// and the weight-gradient loader that rebuilds x1 from h1 (ffn_wgrad_bf16_kernel<true>) both call
+// this, so both compile to the same operations and x1 has the same bits in either place.
+__device__ __forceinline__ float ln_apply(float h, float mu, float rs, float g, float b) {
+  return (h - mu) * rs * g + b;
+}
+
+// h = drop(acc + bias) + res -> hrow; y = LayerNorm(h) * gamma + beta -> yrow (STORE_Y) and yv;
+// mean / rstd of row m. Lane (r, q) holds row m's columns 16t + 4q + e; two xor shuffles complete
+// the row sums. Same per-element order as rs_gemm_add_layernorm (gemm_stream.hip ln_epilogue).
+// base = m * D + 4q: the dropout element index (host: M * D < 2^32).
+template <bool DROP, bool STORE_Y>
+__device__ __forceinline__ void add_ln64(const floatx4 (&acc)[4], const floatx4 (&res)[4], const float* sb,
+                                         const float* sg, const float* sbt, const DropKey& k, uint32_t base,
+                                         int q, float eps, float* hrow, float* yrow, float* mean,
+                                         float* rstd, floatx4 (&yv)[4]) {
+  float hv[4][4];
+  float s = 0.f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int n0 = 16 * t + 4 * q;
+    const floatx4 bv = *reinterpret_cast<const floatx4*>(sb + n0);
+    float mk[4];
+    if constexpr (DROP) keep4_32(k, base + 16 * t, mk);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float v = acc[t][e] * 1.0f + bv[e];
+      if constexpr (DROP) v *= mk[e];
+      hv[t][e] = v + res[t][e];
+      s += hv[t][e];
+    }
+  }
+  s += __shfl_xor(s, 16, 64);
+  s += __shfl_xor(s, 32, 64);
+  const float mu = s / (float)D;
+  float vs = 0.f;
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float d = hv[t][e] - mu;
+      vs += d * d;
+    }
+  vs += __shfl_xor(vs, 16, 64);
+  vs += __shfl_xor(vs, 32, 64);
+  const float rs = 1.f / sqrtf(vs / (float)D + eps);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    const int n0 = 16 * t + 4 * q;
+    const floatx4 gm = *reinterpret_cast<const floatx4*>(sg + n0);
+    const floatx4 bt = *reinterpret_cast<const floatx4*>(sbt + n0);
+    floatx4 h4, y4;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      h4[e] = hv[t][e];
+      y4[e] = ln_apply(hv[t][e], mu, rs, gm[e], bt[e]);
+    }
+    *reinterpret_cast<floatx4*>(hrow + n0) = h4;
+    if constexpr (STORE_Y) *reinterpret_cast<floatx4*>(yrow + n0) = y4;
+    yv[t] = y4;
+  }
+  if (q == 0) {
+    *mean = mu;
+    *rstd = rs;
+  }
+}
+
 template <int F, bool DROP>
 __global__ __launch_bounds__(512) void ffn_fwd_bf16_kernel(FfnArgs a) {
   constexpr int FP = F + 8;
-  constexpr int NH = F / 16, NC = F / 32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   __bf16* W1s = reinterpret_cast<__bf16*>(smem_raw);  // [F][DP]
   __bf16* W2p = W1s + F * DP;                           // [D][FP], k-permuted
@@ -162,92 +277,144 @@ __global__ __launch_bounds__(512) void ffn_fwd_bf16_kernel(FfnArgs a) {
     load_row64(a.x, (int64_t)gn * 16 + r, q, xr);
     // dropout element indices m*F + n / m*D + n in 32 bits (host: M*F < 2^32)
     const uint32_t base1 = (uint32_t)m * F + 4 * q, base2 = (uint32_t)m * D + 4 * q;
-    // linear1 + bias + relu + dropout, 4 tiles at a time, into linear2's operand fragments
-    bf16x8 a2[NC];
-    uint64_t bits = 0;
-#pragma unroll
-    for (int h0 = 0; h0 < NH; h0 += 4) {
-      floatx4 acc[4];
-#pragma unroll
-      for (int hh = 0; hh < 4; ++hh) {
-        acc[hh] = floatx4{0.f, 0.f, 0.f, 0.f};
-        RS_MFMA2(acc[hh], W1i, DP, (h0 + hh) * 16 + r, af);
-      }
-#pragma unroll
-      for (int hh = 0; hh < 4; ++hh) {
-        const int h = h0 + hh, n0 = 16 * h + 4 * q;
-        const floatx4 bv = *reinterpret_cast<const floatx4*>(sb1 + n0);
-        float mk[4];
-        if constexpr (DROP) keep4_32(k1, base1 + 16 * h, mk);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          float v = acc[hh][i] * 1.0f + bv[i];
-          v = fmaxf(v, 0.f);
-          if constexpr (DROP) v *= mk[i];
-          if (v > 0.f) bits |= 1ull << (4 * h + i);
-          a2[h >> 1][4 * (h & 1) + i] = (__bf16)v;
-        }
-      }
-    }
+    uint64_t bits;
+    floatx4 acc2[4], yv[4];
+    ffn_products<F, DROP>(af, W1i, W2i, sb1, k1, base1, r, q, bits, acc2);
     a.mask[m * (F / 64) + q] = bits;  // F == 256: one word per lane quad
-    // linear2 over the permuted k slices
-    floatx4 acc2[4];
+    // bias + dropout2 + residual + LayerNorm
+    add_ln64<DROP, true>(acc2, res, sb2, sg, sbt, k2, base2, q, a.eps, a.h + m * D, a.y + m * D, a.mean + m,
+                         a.rstd + m, yv);
+  }
+}
+
+// The encoder layer's forward tail in one kernel per 16-row group (rs_layer_tail_fwd_bf16):
+//   h1 = x + drop1(att Wo^T + bo), x1 = LN1(h1)            (rowgemm_bf16_kernel<4, 1, true, ..>)
+//   x2 = LN2(x1 + drop2(linear2(drop(relu(linear1(x1))))))   (ffn_fwd_bf16_kernel)
+//   qkv = bf16(x2) Win^T + bin  as bf16 (QKV)               (rowgemm_bf16_kernel<12, 1, false, 1, 2>)
+// x1 and x2 go from one product's epilogue layout to the next one's operand layout through a
+// per-wave LDS tile (chain.h) instead of through HBM; each part keeps the operation order of the
+// kernel it replaces, so every output has that chain's bits. The residual row of output row m is
+// resid row m, or row m * bag + rows[m] (ROWS: the pruned last layer's x[b, last[b]]).
+struct TailArgs {
+  FfnArgs f;  // W1 .. beta, eps: the FFN and LN2; h, y, mean, rstd: h2, x2, mean2, rstd2; x unused
+  const float* att;
+  const float* Wo; int ldwo;
+  const float* bo;
+  const float* resid;
+  const int64_t* rows; int bag;
+  const float* gamma1;
+  const float* beta1;
+  float eps1;
+  float* h1;
+  float* x1;
+  float* mean1;
+  float* rstd1;
+  int site0;  // dropout1's site
+  const float* Win; int ldwin;
+  const float* bin;
+  __bf16* qkv;  // [M, 192]
+};
+
+// X1: x1 is also stored (the weight gradients then read it; without it they rebuild it from h1,
+// rs_ffn_wgrad_ln_bf16)
+template <int F, bool DROP, bool QKV, bool X1>
+__global__ __launch_bounds__(512) void layer_tail_fwd_bf16_kernel(TailArgs a) {
+  constexpr int FP = F + 8;
+  static_assert(DP == CH_DP && D == CH_D, "chain.h's tile is the [*][D] image");
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __bf16* W1s = reinterpret_cast<__bf16*>(smem_raw);  // [F][DP]
+  __bf16* W2p = W1s + F * DP;                           // [D][FP], k-permuted
+  __bf16* Wos = W2p + D * FP;                           // [D][DP]
+  __bf16* tiles = Wos + D * DP;                         // [8 waves][16][DP]
+  float* sb1 = reinterpret_cast<float*>(tiles + 8 * 16 * DP);  // [F]
+  float* sb2 = sb1 + F;                                 // [D] each from here
+  float* sg = sb2 + D;
+  float* sbt = sg + D;
+  float* sbo = sbt + D;
+  float* sg1 = sbo + D;
+  float* sbt1 = sg1 + D;
+  float* sbin = sbt1 + D;                                     // [192]  (QKV)
+  __bf16* Wins = reinterpret_cast<__bf16*>(sbin + 3 * D);     // [192][DP]  (QKV)
+  const FfnArgs& f = a.f;
+  stage_batched<F, D, 512>(f.W1, D, [&](int n, int k, const floatx4& v) { put4(W1s + n * DP + k, v); });
+  stage_batched<D, F, 512>(f.W2, F, [&](int n, int k, const floatx4& v) { put4(W2p + n * FP + kslot(k), v); });
+  stage_batched<D, D, 512>(a.Wo, a.ldwo, [&](int n, int k, const floatx4& v) { put4(Wos + n * DP + k, v); });
+  if constexpr (QKV)
+    stage_batched<3 * D, D, 512>(a.Win, a.ldwin, [&](int n, int k, const floatx4& v) { put4(Wins + n * DP + k, v); });
+  for (int i = threadIdx.x; i < F; i += blockDim.x) sb1[i] = f.b1[i];
+  for (int i = threadIdx.x; i < D; i += blockDim.x) {
+    sb2[i] = f.b2[i];
+    sg[i] = f.gamma[i];
+    sbt[i] = f.beta[i];
+    sbo[i] = a.bo[i];
+    sg1[i] = a.gamma1[i];
+    sbt1[i] = a.beta1[i];
+  }
+  if constexpr (QKV)
+    for (int i = threadIdx.x; i < 3 * D; i += blockDim.x) sbin[i] = a.bin[i];
+  __syncthreads();
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int groups = f.M / 16;  // host: M % 16 == 0
+  DropKey k0{}, k1{}, k2{};
+  if constexpr (DROP) {
+    k0 = make_key(f.key, a.site0, f.p);
+    k1 = make_key(f.key, f.site1, f.p);
+    k2 = make_key(f.key, f.site2, f.p);
+  }
+  __bf16* tile = tiles + (wave * 16 + r) * DP;
+  const int stride = gridDim.x * 8;
+  int g = blockIdx.x * 8 + wave;
+  // this group's att row (operand layout) and residual row (epilogue layout), one step ahead
+  auto resid_row = [&](int64_t m) {
+    return a.resid + (a.rows ? m * a.bag + a.rows[m] : m) * D + 4 * q;
+  };
+  floatx4 ar[4], rr[4];
+  if (g < groups) {
+    load_row64(a.att, (int64_t)g * 16 + r, q, ar);
+    const float* rp = resid_row((int64_t)g * 16 + r);
 #pragma unroll
-    for (int t = 0; t < 4; ++t) acc2[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < 4; ++t) rr[t] = *(gptr4)(rp + 16 * t);
+  }
+  for (; g < groups; g += stride) {
+    // an opaque zero offset per iteration keeps the W fragment reads inside the loop
+    int zo = 0;
+    asm volatile("" : "+s"(zo));
+    const __bf16* W1i = W1s + zo;
+    const __bf16* W2i = W2p + zo;
+    const __bf16* Woi = Wos + zo;
+    const int64_t m = (int64_t)g * 16 + r;
+    bf16x8 af[2] = {cvt8(ar[0], ar[1]), cvt8(ar[2], ar[3])};
+    floatx4 res[4];
 #pragma unroll
-    for (int c = 0; c < NC; ++c)
+    for (int t = 0; t < 4; ++t) res[t] = rr[t];
+    {
+      const int gn = g + stride < groups ? g + stride : g;
+      load_row64(a.att, (int64_t)gn * 16 + r, q, ar);
+      const float* rp = resid_row((int64_t)gn * 16 + r);
 #pragma unroll
-      for (int t = 0; t < 4; ++t)
-        acc2[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(lds8(W2i + (16 * t + r) * FP + 32 * c + 8 * q),
-                                                           a2[c], acc2[t], 0, 0, 0);
-    // bias + dropout2 + residual + LayerNorm (same per-element order as rs_gemm_add_layernorm)
-    float hv[4][4];
-    float s = 0.f;
+      for (int t = 0; t < 4; ++t) rr[t] = *(gptr4)(rp + 16 * t);
+    }
+    const uint32_t base1 = (uint32_t)m * F + 4 * q, base2 = (uint32_t)m * D + 4 * q;
+    // out-projection + bias + dropout1 + residual + LN1
+    floatx4 acc[4], x1v[4], x2v[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
-      const int n0 = 16 * t + 4 * q;
-      const floatx4 bv = *reinterpret_cast<const floatx4*>(sb2 + n0);
-      float mk[4];
-      if constexpr (DROP) keep4_32(k2, base2 + 16 * t, mk);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        float v = acc2[t][e] * 1.0f + bv[e];
-        if constexpr (DROP) v *= mk[e];
-        hv[t][e] = v + res[t][e];
-        s += hv[t][e];
-      }
+      acc[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+      RS_MFMA2(acc[t], Woi, DP, 16 * t + r, af);
     }
-    s += __shfl_xor(s, 16, 64);
-    s += __shfl_xor(s, 32, 64);
-    const float mu = s / (float)D;
-    float vs = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = hv[t][e] - mu;
-        vs += d * d;
-      }
-    vs += __shfl_xor(vs, 16, 64);
-    vs += __shfl_xor(vs, 32, 64);
-    const float rs = 1.f / sqrtf(vs / (float)D + a.eps);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      const int n0 = 16 * t + 4 * q;
-      const floatx4 gm = *reinterpret_cast<const floatx4*>(sg + n0);
-      const floatx4 bt = *reinterpret_cast<const floatx4*>(sbt + n0);
-      floatx4 h4, y4;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        h4[e] = hv[t][e];
-        y4[e] = (hv[t][e] - mu) * rs * gm[e] + bt[e];
-      }
-      *reinterpret_cast<floatx4*>(a.h + m * D + n0) = h4;
-      *reinterpret_cast<floatx4*>(a.y + m * D + n0) = y4;
-    }
-    if (q == 0) {
-      a.mean[m] = mu;
-      a.rstd[m] = rs;
+    add_ln64<DROP, X1>(acc, res, sbo, sg1, sbt1, k0, base2, q, a.eps1, a.h1 + m * D,
+                       X1 ? a.x1 + m * D : nullptr, a.mean1 + m, a.rstd1 + m, x1v);
+    // x1: the FFN's operand through the wave's tile, its LayerNorm residual from the registers
+    rows_to_operand(tile, x1v, q, af);
+    uint64_t bits;
+    ffn_products<F, DROP>(af, W1i, W2i, sb1, k1, base1, r, q, bits, acc);
+    f.mask[m * (F / 64) + q] = bits;
+    add_ln64<DROP, true>(acc, x1v, sb2, sg, sbt, k2, base2, q, f.eps, f.h + m * D, f.y + m * D, f.mean + m,
+                         f.rstd + m, x2v);
+    if constexpr (QKV) {
+      rows_to_operand(tile, x2v, q, af);
+      chain_linear_bf16<12>(af, Wins + zo, sbin, r, q, a.qkv + m * (3 * D));
     }
   }
 }
@@ -581,6 +748,9 @@ constexpr int WG_OUT = 2 * WG_F * D + WG_F + D;  // dW1 [F][D], dW2 [D][F], db1 
 
 __device__ __forceinline__ short bf16_bits(float v) { return __builtin_bit_cast(short, (__bf16)v); }
 
+// LNX (rs_ffn_wgrad_ln_bf16): x1 is not read but rebuilt while staging, x1 = LN1(h1) from ln_h,
+// ln_mean, ln_rstd, ln_gamma, ln_beta (ln_apply: the forward's bits); everything else is the same.
+template <bool LNX>
 __global__ __launch_bounds__(512) void ffn_wgrad_bf16_kernel(FfnArgs a, float* ws, int rows_per_block) {
   constexpr int F = WG_F;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
@@ -613,12 +783,25 @@ __global__ __launch_bounds__(512) void ffn_wgrad_bf16_kernel(FfnArgs a, float* w
   floatx4 st[4];
   u32x4 mst = {0u, 0u, 0u, 0u};
   float ysum[4] = {0.f, 0.f, 0.f, 0.f};  // colsum(dff) partials of this thread's 4 columns
+  // LNX: the statistics of this thread's two x rows, and gamma / beta of its 4 columns
+  float lmu[2] = {0.f, 0.f}, lrs[2] = {0.f, 0.f};
+  floatx4 lgm = {0.f, 0.f, 0.f, 0.f}, lbt = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (LNX) {
+    lgm = *(gptr4)(a.ln_gamma + (tid % 16) * 4);
+    lbt = *(gptr4)(a.ln_beta + (tid % 16) * 4);
+  }
   auto load_chunk = [&](int c0) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int s2 = tid + 512 * (i & 1), row = c0 + s2 / 16, col = (s2 % 16) * 4;
-      const float* src = i < 2 ? a.x : a.dff;
+      const float* src = i < 2 ? (LNX ? a.ln_h : a.x) : a.dff;
       st[i] = row < r1 ? *(gptr4)(src + (int64_t)row * D + col) : floatx4{0.f, 0.f, 0.f, 0.f};
+      if constexpr (LNX) {
+        if (i < 2) {  // padded rows: h = 0, mean = 0, rstd = 0 -> beta, cleared in store_chunk
+          lmu[i] = row < r1 ? a.ln_mean[row] : 0.f;
+          lrs[i] = row < r1 ? a.ln_rstd[row] : 0.f;
+        }
+      }
     }
     if (tid < 128) {
       const int row = c0 + tid / 2;
@@ -633,6 +816,13 @@ __global__ __launch_bounds__(512) void ffn_wgrad_bf16_kernel(FfnArgs a, float* w
       if (i >= 2) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) ysum[e] += st[i][e];
+      }
+      if constexpr (LNX) {
+        if (i < 2) {
+          const bool live = lrs[i] != 0.f;  // rstd > 0 on every real row
+#pragma unroll
+          for (int e = 0; e < 4; ++e) st[i][e] = live ? ln_apply(st[i][e], lmu[i], lrs[i], lgm[e], lbt[e]) : 0.f;
+        }
       }
       put4((i < 2 ? Xs : Ds) + (buf * WG_ROWS + row) * WXP + col, st[i]);
     }
@@ -789,6 +979,11 @@ size_t wgrad_fused_lds() { return (size_t)2 * 2 * WG_ROWS * WXP * 2 + (size_t)2 
 #undef RS_MFMA2
 
 size_t fwd_lds(int F) { return (size_t)F * DP * 2 + (size_t)D * (F + 8) * 2 + (size_t)(F + 3 * D) * 4; }
+// + Wo, the LN1 / out-projection vectors, the 8 waves' hand-off tiles and (qkv) Win's bias and image
+size_t tail_lds(int F, bool qkv) {
+  return fwd_lds(F) + (size_t)D * DP * 2 + (size_t)3 * D * 4 + chain_tile_bytes(8) +
+         (qkv ? (size_t)3 * D * 4 + (size_t)3 * D * DP * 2 : 0);
+}
 size_t bwd_lds(int F, bool acts = true) {
   return (size_t)(acts ? 2 : 1) * F * DP * 2 + (size_t)D * (F + 8) * 2 + (size_t)F * 4;
 }
@@ -835,6 +1030,57 @@ extern "C" int rs_ffn_fwd_bf16(int M, int F, const float* x, const float* W1, co
   if (p > 0.f) ffn_fwd_bf16_kernel<256, true><<<bx, 512, lds, as_stream(stream)>>>(a);
   else ffn_fwd_bf16_kernel<256, false><<<bx, 512, lds, as_stream(stream)>>>(a);
   RS_CHECK_LAUNCH("rs_ffn_fwd_bf16");
+  return 0;
+}
+
+extern "C" int rs_layer_tail_fwd_bf16(int M, int F, const float* att, const float* Wo, int ldwo,
+                                      const float* bo, const float* resid, const int64_t* resid_rows,
+                                      int resid_bag, const float* gamma1, const float* beta1, float eps1,
+                                      float* h1, float* x1, float* mean1, float* rstd1, const float* W1,
+                                      const float* b1, const float* W2, const float* b2,
+                                      const float* gamma2, const float* beta2, float eps2, float* h2,
+                                      float* x2, float* mean2, float* rstd2, uint64_t* mask,
+                                      const float* Win, int ldwin, const float* bin, void* qkv, float p,
+                                      const int64_t* key, int site0, int site1, int site2, void* stream) {
+  RS_CHECK_ARG(M >= 0 && M % 16 == 0 && F == 256, "rs_layer_tail_fwd_bf16: need M %% 16 == 0 and F == 256 (M=%d F=%d)", M, F);
+  RS_CHECK_ARG(att && Wo && bo && resid && gamma1 && beta1 && h1 && mean1 && rstd1 && W1 && b1 && W2 &&
+                   b2 && gamma2 && beta2 && h2 && x2 && mean2 && rstd2 && mask,
+               "rs_layer_tail_fwd_bf16: null operand");
+  RS_CHECK_ARG((!Win) == (!qkv) && (!Win) == (!bin), "rs_layer_tail_fwd_bf16: Win, bin and qkv go together");
+  RS_CHECK_ARG(!resid_rows || resid_bag >= 1, "rs_layer_tail_fwd_bf16: resid_rows needs resid_bag >= 1");
+  RS_CHECK_ARG(ldwo >= 64 && ldwo % 4 == 0 && (!Win || (ldwin >= 64 && ldwin % 4 == 0)),
+               "rs_layer_tail_fwd_bf16: bad leading dimension");
+  RS_CHECK_ARG(aligned16(att) && aligned16(Wo) && aligned16(resid) && aligned16(h1) && (!x1 || aligned16(x1)) &&
+                   aligned16(W1) && aligned16(W2) && aligned16(h2) && aligned16(x2) &&
+                   (!Win || (aligned16(Win) && ((uintptr_t)qkv & 7) == 0)),
+               "rs_layer_tail_fwd_bf16: operands must be 16-byte aligned");
+  RS_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || key), "rs_layer_tail_fwd_bf16: dropout needs a key, 0 <= p < 1");
+  RS_CHECK_ARG((int64_t)M * F < ((int64_t)1 << 32), "rs_layer_tail_fwd_bf16: M*F must be < 2^32");
+  if (M == 0) return 0;
+  TailArgs a{};
+  a.f.M = M; a.f.W1 = W1; a.f.b1 = b1; a.f.W2 = W2; a.f.b2 = b2; a.f.gamma = gamma2; a.f.beta = beta2;
+  a.f.eps = eps2; a.f.h = h2; a.f.y = x2; a.f.mean = mean2; a.f.rstd = rstd2; a.f.mask = mask; a.f.p = p;
+  a.f.key = key; a.f.site1 = site1; a.f.site2 = site2;
+  a.att = att; a.Wo = Wo; a.ldwo = ldwo; a.bo = bo; a.resid = resid; a.rows = resid_rows; a.bag = resid_bag;
+  a.gamma1 = gamma1; a.beta1 = beta1; a.eps1 = eps1; a.h1 = h1; a.x1 = x1; a.mean1 = mean1; a.rstd1 = rstd1;
+  a.site0 = site0; a.Win = Win; a.ldwin = ldwin; a.bin = bin; a.qkv = reinterpret_cast<__bf16*>(qkv);
+  const size_t lds = tail_lds(F, qkv != nullptr);
+  const int bx = grid_for(M, lds);
+  hipStream_t st = as_stream(stream);
+#define RS_TAIL(DROPV, QKVV)                                                                \
+  {                                                                                         \
+    if (x1) layer_tail_fwd_bf16_kernel<256, DROPV, QKVV, true><<<bx, 512, lds, st>>>(a);    \
+    else layer_tail_fwd_bf16_kernel<256, DROPV, QKVV, false><<<bx, 512, lds, st>>>(a);      \
+  }
+  if (p > 0.f) {
+    if (qkv) RS_TAIL(true, true)
+    else RS_TAIL(true, false)
+  } else {
+    if (qkv) RS_TAIL(false, true)
+    else RS_TAIL(false, false)
+  }
+#undef RS_TAIL
+  RS_CHECK_LAUNCH("rs_layer_tail_fwd_bf16");
   return 0;
 }
 
@@ -892,7 +1138,8 @@ extern "C" int rs_ffn_bwd_ln2_bf16(int M, int F, const float* x, const float* W1
                                    float* dbeta1, float p, const int64_t* key, int site1, int site2,
                                    float* ws, void* stream) {
   RS_CHECK_ARG(M >= 0 && M % 16 == 0 && F == 256, "rs_ffn_bwd_ln2_bf16: need M %% 16 == 0 and F == 256 (M=%d F=%d)", M, F);
-  RS_CHECK_ARG(x && W1 && b1 && W2 && mask && dy2 && h2 && gamma2 && mean2 && rstd2 && dff && dgamma2 &&
+  // x (x1) is not read: linear1 is not recomputed here (the !ACTS instances); it may be null
+  RS_CHECK_ARG(W1 && b1 && W2 && mask && dy2 && h2 && gamma2 && mean2 && rstd2 && dff && dgamma2 &&
                    dbeta2 && h1 && gamma1 && mean1 && rstd1 && dh1 && dgamma1 && dbeta1 && ws,
                "rs_ffn_bwd_ln2_bf16: null operand");
   // each 16-row group is read and written by one wave: only dh1 may alias dy2
@@ -954,24 +1201,30 @@ extern "C" int64_t rs_ffn_wgrad_ws_bytes(int M, int F) {
   return F == 256 && M > 0 ? (int64_t)wgrad_fused_grid(M) * WG_OUT * (int64_t)sizeof(float) : 0;
 }
 
-extern "C" int rs_ffn_wgrad_bf16(int M, int F, const float* x, const float* W1, const float* b1,
-                                 const float* W2, const uint64_t* mask, const float* dff, float p,
-                                 float* dW1, float* db1, float* dW2, float* db2, float* ws, void* stream) {
-  RS_CHECK_ARG(M >= 0 && M % 16 == 0 && F == 256, "rs_ffn_wgrad_bf16: need M %% 16 == 0 and F == 256 (M=%d F=%d)", M, F);
-  RS_CHECK_ARG(x && W1 && b1 && W2 && mask && dff && dW1 && db1 && dW2 && db2 && (ws || M == 0),
-               "rs_ffn_wgrad_bf16: null operand");
-  RS_CHECK_ARG(aligned16(x) && aligned16(dff) && aligned16(W1) && aligned16(mask),
-               "rs_ffn_wgrad_bf16: misaligned operand");
-  RS_CHECK_ARG(p >= 0.f && p < 1.f, "rs_ffn_wgrad_bf16: 0 <= p < 1");
+// x null: rs_ffn_wgrad_ln_bf16 (x1 = LN1(h1) rebuilt while staging)
+static int ffn_wgrad_launch(const char* name, int M, int F, const float* x, const float* h1, const float* mean1,
+                            const float* rstd1, const float* gamma1, const float* beta1, const float* W1,
+                            const float* b1, const float* W2, const uint64_t* mask, const float* dff, float p,
+                            float* dW1, float* db1, float* dW2, float* db2, float* ws, void* stream) {
+  RS_CHECK_ARG(M >= 0 && M % 16 == 0 && F == 256, "%s: need M %% 16 == 0 and F == 256 (M=%d F=%d)", name, M, F);
+  RS_CHECK_ARG((x || (h1 && mean1 && rstd1 && gamma1 && beta1)) && W1 && b1 && W2 && mask && dff && dW1 && db1 &&
+                   dW2 && db2 && (ws || M == 0),
+               "%s: null operand", name);
+  RS_CHECK_ARG(aligned16(x) && aligned16(h1) && aligned16(gamma1) && aligned16(beta1) && aligned16(dff) &&
+                   aligned16(W1) && aligned16(mask),
+               "%s: misaligned operand", name);
+  RS_CHECK_ARG(p >= 0.f && p < 1.f, "%s: 0 <= p < 1", name);
   if (M == 0) return 0;
   FfnArgs a{};
   a.M = M; a.x = x; a.W1 = W1; a.b1 = b1; a.W2 = W2; a.mask = const_cast<uint64_t*>(mask); a.dff = dff;
   a.p = p;
+  a.ln_h = h1; a.ln_mean = mean1; a.ln_rstd = rstd1; a.ln_gamma = gamma1; a.ln_beta = beta1;
   const int G = wgrad_fused_grid(M);
   const int rpb = cdiv(cdiv(M, WG_ROWS), G) * WG_ROWS;
   hipStream_t st = as_stream(stream);
-  ffn_wgrad_bf16_kernel<<<cdiv(M, rpb), 512, wgrad_fused_lds(), st>>>(a, ws, rpb);
-  RS_CHECK_LAUNCH("rs_ffn_wgrad_bf16");
+  if (x) ffn_wgrad_bf16_kernel<false><<<cdiv(M, rpb), 512, wgrad_fused_lds(), st>>>(a, ws, rpb);
+  else ffn_wgrad_bf16_kernel<true><<<cdiv(M, rpb), 512, wgrad_fused_lds(), st>>>(a, ws, rpb);
+  RS_CHECK_LAUNCH(name);
   if (reduce_deferring()) {  // queued for rs_reduce_flush: dW1 | dW2 | db1 | db2 += the column sums
     constexpr int FD = WG_F * D;
     float* outs[4] = {dW1, dW2, db1, db2};
@@ -981,8 +1234,25 @@ extern "C" int rs_ffn_wgrad_bf16(int M, int F, const float* x, const float* W1, 
     return 0;
   }
   ffn_wgrad_reduce_kernel<<<cdiv(WG_OUT, 64), 1024, 0, st>>>(ws, cdiv(M, rpb), dW1, dW2, db1, db2);
-  RS_CHECK_LAUNCH("rs_ffn_wgrad_bf16 reduce");
+  RS_CHECK_LAUNCH(name);
   return 0;
+}
+
+extern "C" int rs_ffn_wgrad_bf16(int M, int F, const float* x, const float* W1, const float* b1,
+                                 const float* W2, const uint64_t* mask, const float* dff, float p,
+                                 float* dW1, float* db1, float* dW2, float* db2, float* ws, void* stream) {
+  RS_CHECK_ARG(x, "rs_ffn_wgrad_bf16: null operand");
+  return ffn_wgrad_launch("rs_ffn_wgrad_bf16", M, F, x, nullptr, nullptr, nullptr, nullptr, nullptr, W1, b1, W2,
+                          mask, dff, p, dW1, db1, dW2, db2, ws, stream);
+}
+
+extern "C" int rs_ffn_wgrad_ln_bf16(int M, int F, const float* h1, const float* mean1, const float* rstd1,
+                                    const float* gamma1, const float* beta1, const float* W1, const float* b1,
+                                    const float* W2, const uint64_t* mask, const float* dff, float p,
+                                    float* dW1, float* db1, float* dW2, float* db2, float* ws, void* stream) {
+  RS_CHECK_ARG(h1 && mean1 && rstd1 && gamma1 && beta1, "rs_ffn_wgrad_ln_bf16: null operand");
+  return ffn_wgrad_launch("rs_ffn_wgrad_ln_bf16", M, F, nullptr, h1, mean1, rstd1, gamma1, beta1, W1, b1, W2,
+                          mask, dff, p, dW1, db1, dW2, db2, ws, stream);
 }
 
 extern "C" int64_t rs_wgrad_ws_bytes(int Mo, int No, int rows) { return wgrad_ws_bytes(Mo, No, rows); }

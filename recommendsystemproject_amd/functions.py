@@ -404,19 +404,54 @@ def _ffn_fwd(lyr, x1, p, key, site):
     return x2, (f1, h2, m2, r2)
 
 
-def layer_fwd(lyr, x, key_pad, B, L, d, H, p, key, site):
-    """nn.TransformerEncoderLayer (norm_first=False, relu) forward on x [B*L, d]."""
-    sa_mod = lyr.self_attn
+def _in_proj_fwd(sa_mod, x, B, L, d, H):
     # bf16 mode: qkv stored as bf16 (only ever an MFMA operand: same products, half the bytes)
-    qkv = ops.linear_fwd(x, sa_mod.in_proj_weight, sa_mod.in_proj_bias,
-                         out_dtype=torch.bfloat16 if ops.qkv_bf16_ok(L, d, H, B * L) else torch.float32)
+    return ops.linear_fwd(x, sa_mod.in_proj_weight, sa_mod.in_proj_bias,
+                          out_dtype=torch.bfloat16 if ops.qkv_bf16_ok(L, d, H, B * L) else torch.float32)
+
+
+def _tail_ok(lyr, att, x, nxt=None):
+    """The layer's forward tail as one kernel (ops.layer_tail_fwd): every bias of the layer present;
+    nxt: the next layer's attention module when the kernel is also to emit that layer's qkv."""
+    sa_mod = lyr.self_attn
+    return (sa_mod.out_proj.bias is not None and lyr.linear1.bias is not None and lyr.linear2.bias is not None and
+            ops.layer_tail_ok(att, x, lyr.linear1.weight, sa_mod.out_proj.weight,
+                              None if nxt is None else nxt.in_proj_weight))
+
+
+def layer_fwd(lyr, x, key_pad, B, L, d, H, p, key, site, qkv=None, next_attn=None):
+    """nn.TransformerEncoderLayer (norm_first=False, relu) forward on x [B*L, d]. qkv: this layer's
+    packed in-projection when the previous stage already computed it. next_attn: the next layer's
+    attention module; a third value is then returned, that layer's qkv (bf16) from the fused tail
+    kernel, or None where it does not run."""
+    sa_mod = lyr.self_attn
+    if qkv is None:
+        qkv = _in_proj_fwd(sa_mod, x, B, L, d, H)
     att, lse = ops.attn_fwd(qkv, key_pad, B, L, d, H, p, key, site)
+    # the fused tail where the token count is the bf16 streaming kernels' (ops.qkv_bf16_ok); it emits
+    # the next layer's qkv too when that layer has an in-projection bias (else that layer computes it)
+    chain = ops.qkv_bf16_ok(L, d, H, B * L)
+    nxt = next_attn if next_attn is not None and next_attn.in_proj_bias is not None else None
+    if chain and nxt is not None and not _tail_ok(lyr, att, x, nxt):
+        nxt = None  # an in-projection the kernel does not take: the tail without qkv
+    if chain and _tail_ok(lyr, att, x, nxt):
+        # bf16 mode: out-proj + LN1 + FFN + LN2 (+ the next layer's qkv) in one pass; x1 and x2 go
+        # from stage to stage on chip (csrc/ffn.hip rs_layer_tail_fwd_bf16)
+        h1, x1, m1, r1, h2, x2, m2, r2, fmask, qn = ops.layer_tail_fwd(
+            att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, x, lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps,
+            lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, lyr.linear2.bias, lyr.norm2.weight,
+            lyr.norm2.bias, lyr.norm2.eps, p, key, site,
+            Win=None if nxt is None else nxt.in_proj_weight, bin_=None if nxt is None else nxt.in_proj_bias,
+            store_x1=False)  # x1 is None: the weight gradients rebuild it from h1 (ops.ffn_wgrad_ln_bf16)
+        s = (x, qkv, att, lse, h1, x1, m1, r1, ('ffn', fmask), h2, m2, r2)
+        return (x2, s) if next_attn is None else (x2, s, qn)
     # h1 = x + dropout1(out_proj(att)), x1 = norm1(h1): GEMM + residual + LayerNorm in one kernel
     h1, x1, m1, r1 = ops.linear_add_layernorm(att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, x,
                                               lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps, p, key,
                                               site + 1)
     x2, ff = _ffn_fwd(lyr, x1, p, key, site)
-    return x2, (x, qkv, att, lse, h1, x1, m1, r1) + ff
+    s = (x, qkv, att, lse, h1, x1, m1, r1) + ff
+    return (x2, s) if next_attn is None else (x2, s, None)
 
 
 def prune_last_layer() -> bool:
@@ -426,13 +461,13 @@ def prune_last_layer() -> bool:
     return not os.environ.get('RSYS_FULL_LAST_LAYER')
 
 
-def layer_fwd_last(lyr, x, key_pad, last, B, L, d, H, p, key, site):
+def layer_fwd_last(lyr, x, key_pad, last, B, L, d, H, p, key, site, qkv=None):
     """The final encoder layer for the selected rows last[b] only -> x2 [B, d] (= the encoder
-    output): qkv for all rows (every key / value is live), attention of the B selected queries,
-    then out-proj + LN1 + FFN + LN2 on B rows."""
+    output): qkv for all rows (every key / value is live; given, or computed here), attention of
+    the B selected queries, then out-proj + LN1 + FFN + LN2 on B rows."""
     sa_mod = lyr.self_attn
-    qkv = ops.linear_fwd(x, sa_mod.in_proj_weight, sa_mod.in_proj_bias,
-                         out_dtype=torch.bfloat16 if ops.qkv_bf16_ok(L, d, H, B * L) else torch.float32)
+    if qkv is None:
+        qkv = _in_proj_fwd(sa_mod, x, B, L, d, H)
     att, lse = ops.attn_rows_fwd(qkv, key_pad, last, B, L, d, H, p, key, site)
     # the residual rows x[b, last[b]] read in place by the fused kernel (bf16 mode), else gathered
     post = ops.linear_add_layernorm_rows(att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, x, last, L,
@@ -470,9 +505,14 @@ def _post_attn_bwd(lyr, saved, dx2, p, key, site):
             m2, r2, g(lyr.norm2.weight), g(lyr.norm2.bias), h1, lyr.norm1.weight, m1, r1,
             g(lyr.norm1.weight), g(lyr.norm1.bias), p, key, site + 1, site + 3, dsa=not fuse)
         ln1_done = True
-        ops.ffn_wgrad_bf16(x1, lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, f1[1], dff, p,
-                           g(lyr.linear1.weight), g(lyr.linear1.bias), g(lyr.linear2.weight),
-                           g(lyr.linear2.bias))
+        if x1 is None:  # the fused forward tail did not store x1 = LN1(h1): rebuilt while staging
+            ops.ffn_wgrad_ln_bf16(h1, m1, r1, lyr.norm1.weight, lyr.norm1.bias, lyr.linear1.weight,
+                                  lyr.linear1.bias, lyr.linear2.weight, f1[1], dff, p, g(lyr.linear1.weight),
+                                  g(lyr.linear1.bias), g(lyr.linear2.weight), g(lyr.linear2.bias))
+        else:
+            ops.ffn_wgrad_bf16(x1, lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, f1[1], dff, p,
+                               g(lyr.linear1.weight), g(lyr.linear1.bias), g(lyr.linear2.weight),
+                               g(lyr.linear2.bias))
     else:
         dff = torch.empty_like(dx2) if p > 0 else None
         dh2 = ops.layernorm_bwd(h2, dx2, lyr.norm2.weight, m2, r2, g(lyr.norm2.weight), g(lyr.norm2.bias),
@@ -561,17 +601,21 @@ class SeqEncoderFn(torch.autograd.Function):
         p = enc.dropout_p if enc.training else 0.0
         key = ops.rng_next(enc.rng_state) if p > 0 else None
         err = enc.err_flag
-        x, in_saved = seq_input_fwd(proc, seqd, B, L, p, key, err, need)
         layers = list(enc.transformer_backbone.layers)
         if enc.transformer_backbone.norm is not None:
             raise NotImplementedError('TransformerEncoder(norm=...) is not used by the reference')
+        x, in_saved = seq_input_fwd(proc, seqd, B, L, p, key, err, need)
+        qkv = None  # a layer's qkv where the previous layer's fused tail computed it
         prune = prune_last_layer() and len(layers) > 0 and L <= 256
         saved = []
         for i, lyr in enumerate(layers):
             if prune and i == len(layers) - 1:
-                x, s = layer_fwd_last(lyr, x, key_pad, last, B, L, d, H, p, key, _layer_site(i))
+                x, s = layer_fwd_last(lyr, x, key_pad, last, B, L, d, H, p, key, _layer_site(i), qkv=qkv)
+            elif i + 1 < len(layers):
+                x, s, qkv = layer_fwd(lyr, x, key_pad, B, L, d, H, p, key, _layer_site(i), qkv=qkv,
+                                      next_attn=layers[i + 1].self_attn)
             else:
-                x, s = layer_fwd(lyr, x, key_pad, B, L, d, H, p, key, _layer_site(i))
+                x, s = layer_fwd(lyr, x, key_pad, B, L, d, H, p, key, _layer_site(i), qkv=qkv)
             saved.append(s)
         if prune:
             out = x  # [B, d]: the final layer produced the selected rows only

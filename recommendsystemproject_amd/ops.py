@@ -185,12 +185,13 @@ def ffn_bwd_ln2_bf16(x, W1, b1, W2, mask, dy2, h2, gamma2, mean2, rstd2, dgamma2
                      mean1, rstd1, dgamma1, dbeta1, p, key, site1, site2, dsa=True):
     """norm2's backward + the FFN backward + norm1's backward in one pass (weight gradients by
     ffn_wgrad_bf16 from the returned dff): -> (dh1, dsa or None, dff = drop2(dh2)). dsa=False:
-    dsa = drop1(dh1) is not stored (None; outproj_bwd_fused masks dh1 itself)."""
-    M, F = x.shape[0], W1.shape[0]
+    dsa = drop1(dh1) is not stored (None; outproj_bwd_fused masks dh1 itself). x (= x1) is not read
+    by this kernel and may be None (a forward that did not store it)."""
+    M, F = dy2.shape[0], W1.shape[0]
     dff = torch.empty_like(dy2)
     dh1 = torch.empty_like(dy2)
     dsa = torch.empty_like(dy2) if p > 0 and dsa else None
-    w = ws(_hip.lib().rs_ffn_bwd_ln2_ws_bytes(M, F), x.device)
+    w = ws(_hip.lib().rs_ffn_bwd_ln2_ws_bytes(M, F), dy2.device)
     call('rs_ffn_bwd_ln2_bf16', M, F, P(x), P(W1), P(b1), P(W2), P(mask), P(dy2), P(h2), P(gamma2), P(mean2),
          P(rstd2), P(dff), P(dgamma2), P(dbeta2), P(h1), P(gamma1), P(mean1), P(rstd1), P(dh1), P(dsa),
          P(dgamma1), P(dbeta1), float(p), P(key), site1, site2, P(w), stream())
@@ -204,6 +205,16 @@ def ffn_wgrad_bf16(x, W1, b1, W2, mask, dff, p, dW1, db1, dW2, db2):
     w = ws(_hip.lib().rs_ffn_wgrad_ws_bytes(M, F), x.device)
     call('rs_ffn_wgrad_bf16', M, F, P(x), P(W1), P(b1), P(W2), P(mask), P(dff), float(p), P(dW1), P(db1),
          P(dW2), P(db2), P(w), stream())
+
+
+def ffn_wgrad_ln_bf16(h1, mean1, rstd1, gamma1, beta1, W1, b1, W2, mask, dff, p, dW1, db1, dW2, db2):
+    """ffn_wgrad_bf16 with x1 = LN1(h1) rebuilt while the rows are staged instead of read (the
+    forward's bits: csrc/ffn.hip ln_apply), for a forward that did not store x1
+    (rs_ffn_wgrad_ln_bf16)."""
+    M, F = h1.shape[0], W1.shape[0]
+    w = ws(_hip.lib().rs_ffn_wgrad_ws_bytes(M, F), h1.device)
+    call('rs_ffn_wgrad_ln_bf16', M, F, P(h1), P(mean1), P(rstd1), P(gamma1), P(beta1), P(W1), P(b1), P(W2),
+         P(mask), P(dff), float(p), P(dW1), P(db1), P(dW2), P(db2), P(w), stream())
 
 
 def wgrad_bf16(dy, x, dW, *, db=None, beta=1.0):
@@ -460,6 +471,52 @@ def linear_add_layernorm_rows(x, W, bias, table, rows, bag, gamma, beta, eps=1e-
          int(bag), P(h), P(y), P(gamma), P(beta), P(mean), P(rstd), float(eps), float(p), P(key), site,
          precision.gemm_flags(), stream())
     return h, y, mean, rstd
+
+
+def fwd_chain_on() -> bool:
+    """The encoder forward's chained kernels (csrc/chain.h: a Linear computed from the rows the
+    previous stage still holds on chip): bf16 compute mode, RSYS_FWD_CHAIN not 0."""
+    return precision.compute_dtype() == 'bf16' and os.environ.get('RSYS_FWD_CHAIN', '1') != '0'
+
+
+def _rowmajor(W, cols):
+    return W.dim() == 2 and W.shape[1] == cols and W.stride(1) == 1 and W.stride(0) % 4 == 0
+
+
+def layer_tail_ok(att, resid, W1, Wo, Win=None):
+    """The encoder layer's fused forward tail (rs_layer_tail_fwd_bf16): where the fused FFN runs
+    (d = 64, F = 256, rows a multiple of 16) and the out-projection's fused LayerNorm is not
+    switched off (RSYS_UNFUSED_LN), RSYS_FWD_CHAIN not 0."""
+    return (fwd_chain_on() and ffn_supported(att, W1) and att.dtype == torch.float32 and
+            resid.dtype == torch.float32 and tuple(resid.shape) == tuple(att.shape) and resid.is_contiguous() and
+            _aligned16(resid) and
+            os.environ.get('RSYS_UNFUSED_LN', '0') in ('', '0') and
+            tuple(Wo.shape) == (64, 64) and _rowmajor(Wo, 64) and _aligned16(att, Wo) and
+            (Win is None or (Win.shape[0] == 192 and _rowmajor(Win, 64) and _aligned16(Win))))
+
+
+def layer_tail_fwd(att, Wo, bo, resid, g1, be1, eps1, W1, b1, W2, b2, g2, be2, eps2, p, key, site,
+                   Win=None, bin_=None, rows=None, bag=0, store_x1=True):
+    """out-proj + dropout1 + residual + LN1 + FFN + LN2 (+ the next layer's qkv when Win is given)
+    in one pass over the rows -> (h1, x1, mean1, rstd1, h2, x2, mean2, rstd2, mask, qkv or None).
+    Dropout sites: site + 1 (dropout1), site + 2, site + 3 (the FFN's). rows / bag: the residual of
+    row m is resid[m * bag + rows[m]]. store_x1 false: x1 is not written (returned as None); the
+    backward rebuilds it from h1, mean1, rstd1 (ffn_wgrad_ln_bf16)."""
+    M = att.shape[0]
+    F = W1.shape[0]
+    dev = att.device
+    h1, h2, x2 = (torch.empty(M, 64, device=dev) for _ in range(3))
+    x1 = torch.empty(M, 64, device=dev) if store_x1 else None
+    m1, r1, m2, r2 = (torch.empty(M, device=dev) for _ in range(4))
+    mask = torch.empty(int(_hip.lib().rs_ffn_mask_words(M, F)), dtype=torch.int64, device=dev)
+    qkv = torch.empty(M, 192, device=dev, dtype=torch.bfloat16) if Win is not None else None
+    if not resid.is_contiguous() or (rows is None and tuple(resid.shape) != (M, 64)):
+        raise RuntimeError('layer_tail_fwd: resid must be a contiguous [M, 64] tensor (or a table with rows)')
+    call('rs_layer_tail_fwd_bf16', M, F, P(att), P(Wo), Wo.stride(0), P(bo), P(resid), P(rows), int(bag),
+         P(g1), P(be1), float(eps1), P(h1), P(x1), P(m1), P(r1), P(W1), P(b1), P(W2), P(b2), P(g2), P(be2),
+         float(eps2), P(h2), P(x2), P(m2), P(r2), P(mask), P(Win), Win.stride(0) if Win is not None else 0,
+         P(bin_), P(qkv), float(p), P(key) if p > 0 else None, site + 1, site + 2, site + 3, stream())
+    return h1, x1, m1, r1, h2, x2, m2, r2, mask, qkv
 
 
 def add_layernorm_fwd(a, b, gamma, beta, eps=1e-5, p=0.0, key=None, site=0):

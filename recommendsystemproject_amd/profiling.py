@@ -179,7 +179,18 @@ def _ffn_bwd_ln2_work(a):
             4.0 * M * 64 * (5 + (1 if a[23] > 0 and a[20] else 0)) + 16.0 * M + M * F / 8.0)
 
 
+def _layer_tail_work(a):
+    M, F = a[0], a[1]
+    x1, qkv = a[13] is not None, a[31] is not None
+    # att, resid read; h1, h2, x2 (+ x1) written; both rows' mean / rstd; mask bits; qkv as bf16
+    return (2.0 * M * 64 * 64 + 4.0 * M * F * 64 + (2.0 * M * 192 * 64 if qkv else 0.0),
+            4.0 * M * 64 * (5 + x1) + 16.0 * M + M * F / 8.0 + (2.0 * M * 192 if qkv else 0.0))
+
+
 WORK = {
+    'rs_layer_tail_fwd_bf16': _layer_tail_work,
+    # h1 and dff read, the statistics, mask bits; linear1 and dff W2 recomputed, two weight gradients
+    'rs_ffn_wgrad_ln_bf16': lambda a: (8.0 * a[0] * a[1] * 64, 8.0 * a[0] * 64 + 8.0 * a[0] + a[0] * a[1] / 8.0),
     'rs_ffn_bwd_ln_bf16': _ffn_bwd_ln_work,
     'rs_ffn_bwd_ln2_bf16': _ffn_bwd_ln2_work,
     'rs_inbatch_ce_fused_fwd': _ce_fused_work,
