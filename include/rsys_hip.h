@@ -873,6 +873,26 @@ int rs_seq_input_bwd_bf16(const float* dx, const float* cat, int ldcat, const fl
 int rs_seq_input_pos_grad(const float* dx, int rows, int N, float p, const int64_t* key, int site_b,
                           float* pos_grad, float* ws, void* stream);
 
+/* ---------------------------------------------------------------- sequence head (bf16 mode)
+ * The sequence input of SequenceEncoder in one pass over the M = B * L token rows, from the ids:
+ *     cat = the per-token features of `segs`, [M,dcat]     = rs_gather_fwd
+ *     x0  = drop_b(drop_a(cat Wp^T + bp) + pos[m % L])     = rs_gemm_f32 (RS_GEMM_BF16, sites a / b)
+ *     qkv = x0 Win^T + bin, bf16 [M,192]                   = rs_gemm_f32, RS_GEMM_C_BF16
+ * cat (contiguous fp32, for the backward) and x0 [M,64] are written once and not read back. Every
+ * output has the bits of the separate calls above on the same inputs; ids outside [0, vocab)
+ * contribute zeros and set *err_flag (nullable) as rs_gather_fwd does.
+ * Segments: RS_SEG_SPARSE or RS_SEG_POOL with mean / sum pooling (bag <= 8) on ordinary tables
+ * (no lazy_last), dim % 4 == 0, 16-byte-aligned tables, vocab * dim < 2^31, covering columns
+ * [0, dcat) without gaps, dcat % 8 == 0, 16 < dcat <= 64, at most 16 table-row loads per
+ * 16-column quarter of cat. M >= 32768, M % 16 == 0, M % L == 0, d == 64, the positional table
+ * [L,64] within the kernel's LDS budget: rs_seq_head_fwd_bf16_supported answers all of it (host
+ * only). */
+int rs_seq_head_fwd_bf16_supported(const rs_feature_seg_t* segs, int nseg, int M, int L, int d, int dcat);
+int rs_seq_head_fwd_bf16(const rs_feature_seg_t* segs, int nseg, int M, int L, int dcat, const float* Wp,
+                         int ldwp, const float* bp, const float* pos, int ldpos, const float* Win,
+                         int ldwin, const float* bin, float* x0, float* cat, void* qkv, int* err_flag,
+                         float p, const int64_t* key, int site_a, int site_b, void* stream);
+
 /* ---------------------------------------------------------------- reductions */
 /* Deferred parameter-gradient reductions (round 5; no reference counterpart -- the optimizer step
  * of training_utils.py:28-60 is the only reader of these gradients). After rs_reduce_defer(1) the

@@ -219,6 +219,9 @@ SIGNATURES = {
     'rs_seq_input_bwd_bf16': (i32, [vp, vp, i32, vp, i32, i32, i32, i32, f32, vp, i32, i32, vp, vp, vp, vp,
                                     vp]),
     'rs_seq_input_pos_grad': (i32, [vp, i32, i32, f32, vp, i32, vp, vp, vp]),
+    'rs_seq_head_fwd_bf16_supported': (i32, [vp, i32, i32, i32, i32, i32]),
+    'rs_seq_head_fwd_bf16': (i32, [vp, i32, i32, i32, i32, vp, i32, vp, vp, i32, vp, i32, vp, vp, vp, vp, vp,
+                                   f32, vp, i32, i32, vp]),
     'rs_dropout_bwd': (i32, [vp, i64, f32, vp, i32, vp]),
 }
 

@@ -348,7 +348,7 @@ extern "C" int rs_gemm_f32(int transA, int transB, int M, int N, int K, float al
     sa.aux = aux; sa.ld_aux = ld_aux; sa.aux_mod = g.aux_mod; sa.rowsum = rowsum; sa.ws = ws;
     sa.transB = transB;
     sa.drop_p = drop_p; sa.drop_key = drop_key; sa.site_a = site_a; sa.site_b = site_b;
-    if (!rowsum && rowgemm_supported(transA, M, N, K, A, lda)) return rowgemm_launch(sa, st);
+    if (!rowsum && rowgemm_supported(transA, M, N, K, A, lda, mode != 0)) return rowgemm_launch(sa, st);
     RS_CHECK_ARG(!io, "rs_gemm_f32: no streaming instance for bf16 A/C storage (M=%d N=%d K=%d)", M, N, K);
     if (ws && wgrad_supported(transA, transB, M, N, K, A, lda, B, ldb, ldc, epilogue))
       return wgrad_launch(sa, st);

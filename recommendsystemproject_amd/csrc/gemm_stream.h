@@ -35,7 +35,8 @@ struct StreamArgs {
   int aux_bag;
 };
 
-bool rowgemm_supported(int transA, int M, int N, int K, const float* A, int lda);
+// bf16: the call is in the bf16 compute mode (RS_GEMM_BF16), which has one more shape
+bool rowgemm_supported(int transA, int M, int N, int K, const float* A, int lda, bool bf16 = false);
 int rowgemm_launch(const StreamArgs& s, hipStream_t st);
 bool rowgemm_ln_supported(int M, int N, int K, const float* A, int lda);
 int rowgemm_ln_launch(const StreamArgs& s, hipStream_t st);

@@ -25,6 +25,7 @@
 #include "gemm_stream.h"
 #include "rng.h"
 #include "mfma.h"
+#include "chain.h"
 #include "stage.h"
 #include "wgrad_tile.h"
 
@@ -861,6 +862,207 @@ __global__ __launch_bounds__(512) void rowgemm_bf16_kernel(StreamArgs a) {
   }
 }
 
+// ------------------------------------------------------------------- sequence head, bf16 MFMA
+// The user tower's sequence input in one pass over the token rows (rs_seq_head_fwd_bf16):
+//   cat = the per-token features gathered from their tables           (gather_fwd_kernel)
+//   x0  = drop_b(drop_a(cat Wp^T + bp) + pos[m % L]), fp32            (rowgemm_bf16_kernel<4, 1, false, 53 / 5>)
+//   qkv = bf16(x0) Win^T + bin, bf16                                  (rowgemm_bf16_kernel<12, 1, false, 1, 2>)
+// rowgemm_bf16_kernel's loop with its A operand built from the ids instead of read from memory:
+// lane (r, q) needs row r of cat at k = 16q .. 16q + 15 (K zero-padded to 64), four 4-column chunks
+// u. Every chunk lies in one feature segment (widths are multiples of 4), so a lane quarter q has
+// a fixed list of table-row loads: one per chunk of a single-id segment, `bag` per chunk of a
+// pooled one, in position order. The host flattens the segments into that list (HeadLoad, NL
+// entries per quarter, dead entries padded with a live one's addresses); the kernel keeps it in
+// LDS. The chain id -> row is two loads deep: ids are fetched two groups ahead and rows one group
+// ahead, as straight-line code (no branch around a load; bad ids read row 0 and are zeroed after).
+// The values are gather_seg's: a pooled chunk is 0 + row_0 + row_1 .. in position order, a mean
+// is that sum divided by (float)bag, an id outside [0, vocab) contributes zeros and raises *err.
+// cat is still written once, fp32, for the backward (a bf16 cat with a bf16-storage loader in
+// seq_input_bwd_bf16_kernel was bitwise but did not clear the step A/B: DESIGN.md §5 round 14); it
+// is not read back here. x0 goes to the in-projection through the wave's LDS tile (chain.h). Each
+// output has the bits of the kernel named above on the same inputs.
+constexpr int SH_MAXLD = 16;  // table-row loads per lane and row group, at most
+
+struct HeadLoad {
+  const int64_t* idp;  // the segment's ids + the bag position: row m's id is idp[m * istride]
+  const float* tp;     // the segment's table + the chunk's first column within its rows
+  int istride, vocab, dim;
+  int flags;  // bits 0-1: the chunk u the row belongs to; 4: live; 8: a single-id segment (plain copy)
+};
+static_assert(sizeof(HeadLoad) == 32, "eight dwords per entry");
+
+struct HeadArgs {
+  HeadLoad ld[4][SH_MAXLD];  // [q][j]
+  float div[4][4];           // [q][u]: the mean's divisor (float)bag; 0: none
+  int M, L, dcat;
+  const float* Wp; int ldwp;
+  const float* bp;
+  const float* pos; int ldpos;
+  const float* Win; int ldwin;
+  const float* bin;
+  float* x0;    // [M][64]
+  __bf16* qkv;  // [M][192]
+  float* cat;   // [M][dcat]
+  int* err;
+  float p;
+  const int64_t* key;
+  int site_a, site_b;
+};
+static_assert(sizeof(HeadArgs) <= 4096, "HeadArgs must fit the kernel-argument segment");
+
+constexpr int SH_KPH = 64 + 8;  // rowgemm_bf16_kernel's KPH at KC = 1
+static_assert(SH_KPH == CH_DP, "one pitch for both weight images");
+
+size_t seq_head_lds(int L, int nl) {
+  return (size_t)64 * SH_KPH * 2 + (size_t)192 * CH_DP * 2 + chain_tile_bytes(8) + (size_t)(64 + 192) * 4 +
+         (size_t)L * 64 * 4 + (size_t)4 * nl * sizeof(HeadLoad) + 16 * 4;
+}
+
+template <int NL, bool DROP>
+__global__ __launch_bounds__(512) void seq_head_fwd_bf16_kernel(HeadArgs a) {
+  constexpr int EPI = RS_EPI_BIAS | RS_EPI_AUX_ADD | (DROP ? RS_EPI_DROP_A | RS_EPI_DROP_B : 0);
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+  __bf16* Wps = reinterpret_cast<__bf16*>(smem_raw);            // [64][SH_KPH], zero for k >= dcat
+  __bf16* Wins = Wps + 64 * SH_KPH;                             // [192][CH_DP]
+  __bf16* tiles = Wins + 192 * CH_DP;                           // [8 waves][16][CH_DP]
+  float* sbp = reinterpret_cast<float*>(tiles + 8 * 16 * CH_DP);  // [64]
+  float* sbin = sbp + 64;                                       // [192]
+  float* spos = sbin + 192;                                     // [L][64]
+  uint32_t* sld = reinterpret_cast<uint32_t*>(spos + a.L * 64);  // HeadLoad [4][NL]
+  float* sdiv = reinterpret_cast<float*>(sld + 4 * NL * 8);     // [4][4]
+  const int tid = threadIdx.x;
+  const int dcat = a.dcat;
+  stage_batched<64, 64, 512>(a.Wp, a.ldwp, [&](int n, int k, const floatx4& v) { put4(Wps + n * SH_KPH + k, v); },
+                             [&](int, int k) { return k < dcat; });
+  stage_batched<192, 64, 512>(a.Win, a.ldwin, [&](int n, int k, const floatx4& v) { put4(Wins + n * CH_DP + k, v); });
+  for (int i = tid; i < 64; i += 512) sbp[i] = a.bp[i];
+  for (int i = tid; i < 192; i += 512) sbin[i] = a.bin[i];
+  for (int i = tid; i < a.L * 64; i += 512) spos[i] = a.pos[(int64_t)(i / 64) * a.ldpos + i % 64];
+  {
+    const uint32_t* src = reinterpret_cast<const uint32_t*>(&a.ld[0][0]);
+    for (int i = tid; i < 4 * NL * 8; i += 512) {
+      const int e = i / 8;
+      sld[i] = src[((e / NL) * SH_MAXLD + e % NL) * 8 + i % 8];
+    }
+    if (tid < 16) sdiv[tid] = a.div[tid / 4][tid % 4];
+  }
+  __syncthreads();
+
+  const int lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 15, q = lane >> 4;
+  const int groups = a.M / 16;  // host: M % 16 == 0
+  DropKey ka{}, kb{};
+  if constexpr (DROP) {
+    ka = make_key(a.key, a.site_a, a.p);
+    kb = make_key(a.key, a.site_b, a.p);
+  }
+  StreamArgs ea{};  // what epi4_ct reads: the row width of the dropout element index
+  ea.N = 64;
+  __bf16* tile = tiles + (wave * 16 + r) * CH_DP;
+  const int stride = gridDim.x * 8;
+  int g = blockIdx.x * 8 + wave;
+  typedef const __attribute__((address_space(1))) floatx4* gptr4;
+  typedef const __attribute__((address_space(1))) int64_t* gptrid;
+
+  floatx4 rw[NL];   // the table rows of the group about to be computed
+  int64_t idn[NL];  // the ids of the group after it
+  uint32_t okm = 0;  // bit j: rw[j] is a live row with an id in range
+  bool bad = false;
+  auto load_ids = [&](const HeadLoad* ld, int gg) {
+    const int64_t m = (int64_t)gg * 16 + r;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) idn[j] = *(gptrid)(ld[j].idp + m * ld[j].istride);
+  };
+  auto load_rows = [&](const HeadLoad* ld) {
+    okm = 0;
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const bool live = (ld[j].flags & 4) != 0;
+      const bool valid = (uint64_t)idn[j] < (uint64_t)ld[j].vocab;
+      bad |= live && !valid;
+      const bool ok = live && valid;
+      okm |= ok ? 1u << j : 0u;
+      const int64_t row = ok ? idn[j] : 0;
+      rw[j] = *(gptr4)(ld[j].tp + row * ld[j].dim);
+    }
+  };
+  if (g < groups) {
+    const HeadLoad* ld = reinterpret_cast<const HeadLoad*>(sld) + q * NL;
+    load_ids(ld, g);
+    load_rows(ld);
+    load_ids(ld, g + stride < groups ? g + stride : g);
+  }
+  for (; g < groups; g += stride) {
+    // an opaque zero offset per iteration keeps the LDS reads (load list, W fragments) in the loop
+    int zo = 0;
+    asm volatile("" : "+s"(zo));
+    const HeadLoad* ld = reinterpret_cast<const HeadLoad*>(sld + zo) + q * NL;
+    const int m = g * 16 + r;
+    // this group's rows -> the four chunks of the operand
+    floatx4 c4[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) c4[u] = floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < NL; ++j) {
+      const int fl = ld[j].flags;
+      const floatx4 v = (okm >> j & 1u) ? rw[j] : floatx4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const floatx4 nv = (fl & 8) ? v : c4[u] + v;
+        c4[u] = (fl & 4) && (fl & 3) == u ? nv : c4[u];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      const float n = sdiv[zo + q * 4 + u];
+      const floatx4 dv = c4[u] / n;
+      c4[u] = n > 0.f ? dv : c4[u];
+    }
+    const bf16x8 af[2] = {cvt8(c4[0], c4[1]), cvt8(c4[2], c4[3])};
+    // the next group's rows from its ids, then the ids of the group after that (no branch)
+    load_rows(ld);
+    {
+      const int g2 = g + 2 * stride < groups ? g + 2 * stride : g;
+      load_ids(ld, g2);
+    }
+    // cat for the backward, the fp32 values before rounding (what the gather would have written)
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (16 * q + 4 * u < dcat) *reinterpret_cast<floatx4*>(a.cat + (int64_t)m * dcat + 16 * q + 4 * u) = c4[u];
+    // projection, rowgemm_bf16_kernel<4, 1>'s products and epilogue
+    floatx4 acc[4], xv[4];
+    {
+      __builtin_amdgcn_sched_barrier(0);
+      bf16x8 b[4][2];
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        acc[h] = floatx4{0.f, 0.f, 0.f, 0.f};
+        const __bf16* bp = Wps + zo + (h * 16 + r) * SH_KPH + 16 * q;
+        b[h][0] = *reinterpret_cast<const bf16x8*>(bp);
+        b[h][1] = *reinterpret_cast<const bf16x8*>(bp + 8);
+      }
+#pragma unroll
+      for (int u = 0; u < 2; ++u)
+#pragma unroll
+        for (int h = 0; h < 4; ++h)
+          acc[h] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[h][u], af[u], acc[h], 0, 0, 0);
+#pragma unroll
+      for (int h = 0; h < 4; ++h) {
+        const int nl = h * 16 + 4 * q;
+        const floatx4 biasv = *reinterpret_cast<const floatx4*>(sbp + zo + nl);
+        const floatx4 auxv = *reinterpret_cast<const floatx4*>(spos + zo + (m % a.L) * 64 + nl);
+        xv[h] = epi4_ct<EPI>(ea, m, nl, acc[h], ka, kb, biasv, auxv, floatx4{0.f, 0.f, 0.f, 0.f});
+        *reinterpret_cast<floatx4*>(a.x0 + (int64_t)m * 64 + nl) = xv[h];
+      }
+    }
+    // x0 -> the in-projection's operand through the wave's tile, qkv as bf16
+    bf16x8 xf[2];
+    rows_to_operand(tile, xv, q, xf);
+    chain_linear_bf16<12>(xf, Wins + zo, sbin + zo, r, q, a.qkv + (int64_t)m * 192);
+  }
+  if (bad && a.err) atomicOr(a.err, 1);
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------ dispatch
@@ -887,10 +1089,13 @@ int stream_grid(int groups, int per_cu, int min_per_wg = 40) {
   return bx < 1 ? 1 : bx;
 }
 
-bool rowgemm_supported(int transA, int M, int N, int K, const float* A, int lda) {
+bool rowgemm_supported(int transA, int M, int N, int K, const float* A, int lda, bool bf16) {
   if (transA || M < 1024 || K < 4 || K > 256 || N < 1 || N > 256) return false;
   if (K % 4 != 0 || lda % 4 != 0 || !aligned16(A)) return false;
   const int nt = M < kSmallM ? kSmallNT : (N + 15) / 16, kt = (K + 15) / 16;
+  // a sequence projection from 32 feature columns (one 32-wide id feature): bf16 mode only, where
+  // the K = 64 instance zero-pads it like K = 40 and the fused sequence head has its bits
+  if (bf16 && nt == 4 && kt == 2) return true;
   // instantiated (NT, KT) pairs: the encoder/projection shapes and the small-M MLP shapes
   switch (nt * 100 + kt) {
     case 403: case 404: case 412: case 416: case 1204: case 1604: case 304: case 1216:
@@ -978,6 +1183,7 @@ int rowgemm_launch(const StreamArgs& s_in, hipStream_t st) {
     RS_RG(4, 3) RS_RG(4, 4) RS_RG(4, 12) RS_RG(4, 16) RS_RG(12, 4) RS_RG(16, 4) RS_RG(3, 4)
     RS_RG(12, 16) RS_RG(2, 4) RS_RG(8, 4) RS_RG(4, 8) RS_RG(8, 8) RS_RG(16, 8)
     RS_RG(2, 3) RS_RG(2, 8) RS_RG(2, 11) RS_RG(2, 12) RS_RG(2, 16) RS_RG(4, 5) RS_RG(5, 4)
+    RS_RG(4, 2)  // bf16 mode's K = 32 shape with an epilogue the bf16 instances do not have
     default: set_error("rowgemm: no instance for N=%d K=%d", s.N, s.K); return -1;
   }
 #undef RS_RG
@@ -1147,4 +1353,117 @@ int wgrad_launch(const StreamArgs& s, hipStream_t st) {
   return 0;
 }
 
+// ----------------------------------------------------------------------------- sequence head
+namespace {
+
+// The load list of seq_head_fwd_bf16_kernel from the feature segments: the loads per lane quarter
+// it needs (the kernel instance is the smallest NL that holds them), or -1 where the kernel does
+// not take the schema. `out` (nullable) receives the list and the mean divisors.
+int seq_head_plan(const rs_feature_seg_t* segs, int nseg, int dcat, HeadArgs* out) {
+  // dcat % 8 == 0: the widths the one-pass backward (rs_seq_input_bwd_bf16) takes
+  if (!segs || nseg < 1 || dcat < 8 || dcat > 64 || dcat % 8 != 0) return -1;
+  int owner[16];
+  for (int c = 0; c < 16; ++c) owner[c] = -1;
+  for (int s = 0; s < nseg; ++s) {
+    const rs_feature_seg_t& g = segs[s];
+    const bool pool = g.kind == RS_SEG_POOL;
+    if (g.kind != RS_SEG_SPARSE && !(pool && (g.pool_mode == RS_POOL_MEAN || g.pool_mode == RS_POOL_SUM))) return -1;
+    if (g.dim < 4 || g.dim % 4 != 0 || g.out_col < 0 || g.out_col % 4 != 0 || g.out_col + g.dim > dcat) return -1;
+    if (pool && (g.bag < 1 || g.bag > 8)) return -1;
+    if (!g.idx || !g.table || !aligned16(g.table) || g.lazy_last) return -1;
+    if (g.vocab < 1 || g.vocab * g.dim >= ((int64_t)1 << 31)) return -1;
+    if (g.idx_stride < (pool ? g.bag : 1) || g.idx_stride >= ((int64_t)1 << 31)) return -1;
+    for (int c = g.out_col / 4; c < (g.out_col + g.dim) / 4; ++c) {
+      if (owner[c] >= 0) return -1;  // overlapping segments
+      owner[c] = s;
+    }
+  }
+  int cnt[4] = {0, 0, 0, 0};
+  HeadLoad first{};
+  for (int c = 0; c < dcat / 4; ++c) {
+    if (owner[c] < 0) return -1;  // a column no segment writes
+    const rs_feature_seg_t& g = segs[owner[c]];
+    const bool pool = g.kind == RS_SEG_POOL;
+    const int q = c / 4, u = c % 4, bag = pool ? g.bag : 1;
+    if (cnt[q] + bag > SH_MAXLD) return -1;
+    for (int l = 0; l < bag; ++l) {
+      HeadLoad e{};
+      e.idp = g.idx + l;
+      e.tp = g.table + (4 * c - g.out_col);
+      e.istride = (int)g.idx_stride; e.vocab = (int)g.vocab; e.dim = g.dim;
+      e.flags = u | 4 | (pool ? 0 : 8);
+      if (c == 0 && l == 0) first = e;
+      if (out) out->ld[q][cnt[q]] = e;
+      ++cnt[q];
+    }
+    if (out) out->div[q][u] = pool && g.pool_mode == RS_POOL_MEAN ? (float)g.bag : 0.f;
+  }
+  first.flags = 0;  // dead entries: a live one's addresses, no contribution
+  int need = 0;
+  for (int q = 0; q < 4; ++q) {
+    need = cnt[q] > need ? cnt[q] : need;
+    if (out)
+      for (int j = cnt[q]; j < SH_MAXLD; ++j) out->ld[q][j] = first;
+  }
+  return need;
+}
+
+int seq_head_instance(int need) { return need <= 4 ? 4 : (need <= 6 ? 6 : (need <= 8 ? 8 : SH_MAXLD)); }
+
+// two workgroups per CU (the id -> row -> product chain is longer than one covers): the images,
+// the positional table and the 8 waves' tiles within half of the CU's 160 KB
+// dcat > 16: the widths whose separate projection is rowgemm_bf16_kernel<4, 1> (rowgemm_supported)
+bool seq_head_shape_ok(int M, int L, int d, int dcat, int need) {
+  return need >= 1 && d == 64 && M >= kSmallM && M % 16 == 0 && L >= 1 && M % L == 0 && dcat > 16 &&
+         seq_head_lds(L, seq_head_instance(need)) <= 80 * 1024 && dcat % 8 == 0;
+}
+
+}  // namespace
+
 }  // namespace rs
+
+using namespace rs;
+
+extern "C" int rs_seq_head_fwd_bf16_supported(const rs_feature_seg_t* segs, int nseg, int M, int L, int d,
+                                              int dcat) {
+  return seq_head_shape_ok(M, L, d, dcat, seq_head_plan(segs, nseg, dcat, nullptr)) ? 1 : 0;
+}
+
+extern "C" int rs_seq_head_fwd_bf16(const rs_feature_seg_t* segs, int nseg, int M, int L, int dcat,
+                                    const float* Wp, int ldwp, const float* bp, const float* pos, int ldpos,
+                                    const float* Win, int ldwin, const float* bin, float* x0, float* cat,
+                                    void* qkv, int* err_flag, float p, const int64_t* key, int site_a,
+                                    int site_b, void* stream) {
+  HeadArgs a{};
+  const int need = seq_head_plan(segs, nseg, dcat, &a);
+  RS_CHECK_ARG(seq_head_shape_ok(M, L, 64, dcat, need),
+               "rs_seq_head_fwd_bf16: unsupported schema or shape (M=%d L=%d dcat=%d nseg=%d)", M, L, dcat, nseg);
+  RS_CHECK_ARG(Wp && bp && pos && Win && bin && x0 && cat && qkv, "rs_seq_head_fwd_bf16: null operand");
+  RS_CHECK_ARG(ldwp >= dcat && ldwp % 4 == 0 && ldpos >= 64 && ldwin >= 64 && ldwin % 4 == 0,
+               "rs_seq_head_fwd_bf16: bad leading dimension");
+  RS_CHECK_ARG(aligned16(Wp) && aligned16(Win) && aligned16(x0) && aligned16(cat) && aligned16(qkv),
+               "rs_seq_head_fwd_bf16: operands must be 16-byte aligned");
+  RS_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || key), "rs_seq_head_fwd_bf16: dropout needs a key, 0 <= p < 1");
+  a.M = M; a.L = L; a.dcat = dcat;
+  a.Wp = Wp; a.ldwp = ldwp; a.bp = bp; a.pos = pos; a.ldpos = ldpos;
+  a.Win = Win; a.ldwin = ldwin; a.bin = bin;
+  a.x0 = x0; a.cat = cat; a.qkv = reinterpret_cast<__bf16*>(qkv);
+  a.err = err_flag; a.p = p; a.key = key; a.site_a = site_a; a.site_b = site_b;
+  const int nl = seq_head_instance(need);
+  const size_t lds = seq_head_lds(L, nl);
+  // the widest list's instance holds one workgroup per CU in registers
+  const int bx = stream_grid(M / 16, nl > 8 ? 1 : 2, 20);
+  hipStream_t st = as_stream(stream);
+#define RS_SH(NLV)                                                                      \
+  case NLV:                                                                              \
+    if (p > 0.f) seq_head_fwd_bf16_kernel<NLV, true><<<bx, 512, lds, st>>>(a);           \
+    else seq_head_fwd_bf16_kernel<NLV, false><<<bx, 512, lds, st>>>(a);                  \
+    break;
+  switch (nl) {
+    RS_SH(4) RS_SH(6) RS_SH(8)
+    default: RS_SH(SH_MAXLD)
+  }
+#undef RS_SH
+  RS_CHECK_LAUNCH("rs_seq_head_fwd_bf16");
+  return 0;
+}

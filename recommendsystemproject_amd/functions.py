@@ -294,23 +294,33 @@ def seq_feature_segments(proc, seqd, B, L):
     return segs, tables, col, keep
 
 
-def seq_input_fwd(proc, seqd, B, L, p, key, err, need=True):
-    """gather -> Linear(sum dims -> d) -> Dropout -> + pos_emb -> F.dropout (T5). Returns x [B*L, d]."""
+def seq_input_fwd(proc, seqd, B, L, p, key, err, need=True, attn=None):
+    """gather -> Linear(sum dims -> d) -> Dropout -> + pos_emb -> F.dropout (T5). Returns
+    (x [B*L, d], the backward's saved state, qkv0). attn: the first encoder layer's attention
+    module; where the fused sequence head takes the call (ops.seq_head_ok) one kernel does all of
+    it from the ids and also emits that layer's packed in-projection qkv0 (bf16): cat is written
+    for the backward but not read back, x0 is not read back either. Otherwise qkv0 is None."""
     segs, tables, dcat, keep = seq_feature_segments(proc, seqd, B, L)
     if dcat != proc.feature_projection[0].in_features:
         raise RuntimeError(f'mat1 and mat2 shapes cannot be multiplied ({B * L}x{dcat} and '
                            f'{proc.feature_projection[0].in_features}x{proc.target_dim})')
     M = B * L
     dev = proc.pos_emb.weight.device
-    cat = torch.empty(M, dcat, device=dev, dtype=torch.float32)
     calls, lazy = _lookup_lazy(segs, tables, M, keep, record=need, err=err)
-    ops.gather_fwd(segs, M, cat, err, lazy=lazy)
     lin = proc.feature_projection[0]
     pos = proc.pos_emb.weight
+    # ordinary tables only: no lazy-Adam call (catch-up, sharded rows, data-parallel exchange)
+    plain = not calls and lazy is None and not any(hasattr(t, '_rs_lazy') for t in tables)
+    if attn is not None and plain and ops.seq_head_ok(segs, M, L, dcat, lin, pos, attn):
+        x, cat, qkv = ops.seq_head_fwd(segs, M, L, dcat, lin.weight, lin.bias, pos, attn.in_proj_weight,
+                                       attn.in_proj_bias, err, p, key, 0, 1)
+        return x, (segs, tables, cat, keep, calls), qkv
+    cat = torch.empty(M, dcat, device=dev, dtype=torch.float32)
+    ops.gather_fwd(segs, M, cat, err, lazy=lazy)
     # drop_b(drop_a(cat W^T + b) + pos[l]) in the GEMM epilogue (sites 0, 1 = rs_dropout masks)
     x = ops.linear_fwd(cat, lin.weight, lin.bias, aux=pos, aux_mod=L, drop_p=p, drop_key=key,
                        site_a=0, site_b=1)
-    return x, (segs, tables, cat, keep, calls)
+    return x, (segs, tables, cat, keep, calls), None
 
 
 def seq_input_grads(dx, cat, W, B, L, p, key, dW, db, pos_g, consume=True):
@@ -365,7 +375,7 @@ class SeqFeaturesFn(torch.autograd.Function):
             raise IndexError('index out of range in self')
         p = proc.dropout if proc.training else 0.0
         key = ops.rng_next(proc.rng_state) if p > 0 else None
-        x, saved = seq_input_fwd(proc, seqd, B, L, p, key, proc.err_flag, need)
+        x, saved, _ = seq_input_fwd(proc, seqd, B, L, p, key, proc.err_flag, need)
         if need:
             ctx.proc, ctx.saved, ctx.B, ctx.L, ctx.p, ctx.key = proc, saved, B, L, p, key
             ctx.params = params
@@ -604,8 +614,10 @@ class SeqEncoderFn(torch.autograd.Function):
         layers = list(enc.transformer_backbone.layers)
         if enc.transformer_backbone.norm is not None:
             raise NotImplementedError('TransformerEncoder(norm=...) is not used by the reference')
-        x, in_saved = seq_input_fwd(proc, seqd, B, L, p, key, err, need)
-        qkv = None  # a layer's qkv where the previous layer's fused tail computed it
+        # qkv: a layer's in-projection where the stage before it computed it (the fused sequence
+        # head for layer 0, the previous layer's fused tail after that)
+        x, in_saved, qkv = seq_input_fwd(proc, seqd, B, L, p, key, err, need,
+                                         attn=layers[0].self_attn if layers else None)
         prune = prune_last_layer() and len(layers) > 0 and L <= 256
         saved = []
         for i, lyr in enumerate(layers):

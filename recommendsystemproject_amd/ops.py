@@ -593,6 +593,42 @@ def seq_input_bwd_fused(dx, cat, W, L, p, key, site_a, site_b, dW, db, pos_grad)
     return out
 
 
+def seq_head_ok(segs, M, L, dcat, lin, pos, attn):
+    """The fused sequence head (rs_seq_head_fwd_bf16: gather + projection + layer 0's in-projection
+    in one kernel): bf16 compute mode with the chained forward on (fwd_chain_on), bf16 qkv
+    (qkv_bf16_ok), d = 64, a schema and shape the kernel takes (rs_seq_head_fwd_bf16_supported:
+    single-id or mean / sum pooled segments on ordinary tables, widths multiples of 4, dcat <= 64,
+    bag <= 8, the positional table within its LDS budget), both biases present, and
+    RSYS_SEQ_HEAD_FUSED not 0. The caller checks that no segment is a lazy-Adam call."""
+    if os.environ.get('RSYS_SEQ_HEAD_FUSED', '1') == '0' or not fwd_chain_on():
+        return False
+    W, Win = lin.weight, attn.in_proj_weight
+    d = W.shape[0]
+    if lin.bias is None or attn.in_proj_bias is None or Win is None or d != 64 or attn.embed_dim != d:
+        return False
+    if not qkv_bf16_ok(L, d, attn.num_heads, M):
+        return False
+    lib = _hip.lib()
+    return (tuple(W.shape) == (64, dcat) and _rowmajor(W, dcat) and tuple(Win.shape) == (192, 64) and
+            _rowmajor(Win, 64) and _aligned16(W, Win) and pos.dim() == 2 and pos.shape[1] == 64 and
+            pos.stride(1) == 1 and pos.shape[0] >= L and
+            all(t.dtype == torch.float32 for t in (W, Win, pos, lin.bias, attn.in_proj_bias)) and
+            bool(lib.rs_seq_head_fwd_bf16_supported(segments_array(segs), len(segs), M, L, d, dcat)))
+
+
+def seq_head_fwd(segs, M, L, dcat, W, b, pos, Win, bin_, err_flag, p, key, site_a, site_b):
+    """cat [M, dcat] (the gathered features, fp32), x0 = drop_b(drop_a(cat W^T + b) + pos[m % L])
+    (fp32) and qkv0 = x0 Win^T + bin (bf16) from the segments' ids in one kernel -> (x0, cat, qkv0)."""
+    dev = W.device
+    x0 = torch.empty(M, 64, device=dev, dtype=torch.float32)
+    cat = torch.empty(M, dcat, device=dev, dtype=torch.float32)
+    qkv = torch.empty(M, 192, device=dev, dtype=torch.bfloat16)
+    call('rs_seq_head_fwd_bf16', segments_array(segs), len(segs), M, L, dcat, P(W), W.stride(0), P(b), P(pos),
+         pos.stride(0), P(Win), Win.stride(0), P(bin_), P(x0), P(cat), P(qkv), P(err_flag), float(p),
+         P(key) if p > 0 else None, site_a, site_b, stream())
+    return x0, cat, qkv
+
+
 def dropout_bwd(dx, p, key, site):
     call('rs_dropout_bwd', P(dx), dx.numel(), float(p), P(key), site, stream())
     return dx

@@ -187,7 +187,17 @@ def _layer_tail_work(a):
             4.0 * M * 64 * (5 + x1) + 16.0 * M + M * F / 8.0 + (2.0 * M * 192 if qkv else 0.0))
 
 
+def _seq_head_work(a):
+    from . import _hip
+    segs, nseg, M, dcat = a[0], a[1], a[2], a[4]
+    ids = sum(segs[i].bag if segs[i].kind == _hip.RS_SEG_POOL else 1 for i in range(nseg))
+    # the ids read (int64; the tables stay in L2); x0 and cat (fp32) and qkv0 (bf16) written
+    return (2.0 * M * 64 * dcat + 2.0 * M * 192 * 64,
+            8.0 * M * ids + 4.0 * M * 64 + 2.0 * M * 192 + 4.0 * M * dcat)
+
+
 WORK = {
+    'rs_seq_head_fwd_bf16': _seq_head_work,
     'rs_layer_tail_fwd_bf16': _layer_tail_work,
     # h1 and dff read, the statistics, mask bits; linear1 and dff W2 recomputed, two weight gradients
     'rs_ffn_wgrad_ln_bf16': lambda a: (8.0 * a[0] * a[1] * 64, 8.0 * a[0] * 64 + 8.0 * a[0] + a[0] * a[1] / 8.0),
@@ -207,8 +217,7 @@ WORK = {
     'rs_linear_bwd_bf16': lambda a: (4.0 * a[4] * a[5] * a[6],
                                      a[4] * (2.0 * a[5] + 4.0 * a[6] * (3 if a[7] else 2))),
     # one pass: dx read, cat read, dcat written; dW = y^T cat and dcat = y W
-    'rs_seq_input_bwd_bf16': lambda a: (4.0 * a[5] * a[6] * a[7], 4.0 * a[5] * (a[6] + 2 * a[7])),
-    # the out-projection's one pass: dh and att read, datt written; dW = y^T att and datt = y W
+    'rs_seq_input_bwd_bf16': lambda a: (4.0 * a[5] * a[6] * a[7], 4.0 * a[5] * (a[6] + 2 * a[7])),    # the out-projection's one pass: dh and att read, datt written; dW = y^T att and datt = y W
     'rs_outproj_bwd_bf16': lambda a: (4.0 * a[4] * a[5] * a[5], 12.0 * a[4] * a[5]),
     # its companion's second read of dx [rows, N] (one fma per element; the partials are small)
     'rs_seq_input_pos_grad': lambda a: (2.0 * a[1] * a[2], 4.0 * a[1] * a[2]),

@@ -1,0 +1,287 @@
+"""The fused sequence head (csrc/gemm_stream.hip rs_seq_head_fwd_bf16, RSYS_SEQ_HEAD_FUSED): the
+per-token gather, the sequence projection with its dropouts and positional rows, and layer 0's
+in-projection in one kernel, against the three kernels it replaces (rs_gather_fwd and two
+rs_gemm_f32 streaming instances): bitwise, since the operand is built with gather_seg's operations
+and each product keeps its kernel's MFMA order. cat is still written (fp32, the gather's bits)
+for the backward, which is unchanged. Everything the kernel does not take runs the separate
+kernels.
+"""
+import types
+
+import pytest
+import torch
+
+from recommendsystemproject_amd import _hip, functions, ops, precision
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device('cuda:0')
+L = 50
+# B * L = 32,800: the smallest token count the bf16 streaming instances take; 33,200: 2,075 row
+# groups, an odd count that does not divide over the waves
+BATCHES = [656, 664]
+KINDS = ['c2', 'sparse', 'sum']
+
+
+def rnd(*shape, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g).to(DEV)
+
+
+@pytest.fixture
+def bf16_mode():
+    precision.set_compute_dtype('bf16')
+    yield
+    precision.set_compute_dtype('fp32')
+
+
+def _features(kind):
+    """The C2 schema (a 32-wide id feature and an 8-wide tag list of 3, mean pooled), the id
+    feature alone, and the tag list sum pooled. Vocabularies of 97 and 30: rows repeat and the
+    padding id 0 occurs."""
+    feats = [dict(name='hist_movie_ids', vocab_size=97, embedding_dim=32, padding_index=0)]
+    if kind != 'sparse':
+        feats.append(dict(name='hist_genre_ids', vocab_size=30, embedding_dim=8, padding_index=0,
+                          pooling='mean' if kind == 'c2' else 'sum'))
+    return feats
+
+
+def _ids(feats, B, seed=3):
+    g = torch.Generator().manual_seed(seed)
+    out = {}
+    for f in feats:
+        shape = (B, L, 3) if 'pooling' in f else (B, L)
+        out[f['name']] = torch.randint(0, f['vocab_size'], shape, generator=g).to(DEV)
+    return out
+
+
+def _segments(feats, ids, tables):
+    segs, col = [], 0
+    for f in feats:
+        x, D = ids[f['name']], f['embedding_dim']
+        if x.dim() == 2:
+            segs.append(functions._seg(kind=_hip.RS_SEG_SPARSE, dim=D, out_col=col, vocab=f['vocab_size'],
+                                       idx_stride=1, idx=x.data_ptr(), table=tables[f['name']].data_ptr()))
+        else:
+            segs.append(functions._seg(kind=_hip.RS_SEG_POOL, dim=D, out_col=col, pool_mode=_hip.RS_POOL[f['pooling']],
+                                       bag=x.shape[2], vocab=f['vocab_size'], idx_stride=x.shape[2],
+                                       idx=x.data_ptr(), table=tables[f['name']].data_ptr()))
+        col += D
+    return segs, col
+
+
+def _weights(feats):
+    dcat = sum(f['embedding_dim'] for f in feats)
+    tables = {}
+    for i, f in enumerate(feats):
+        t = rnd(f['vocab_size'], f['embedding_dim'], seed=40 + i)
+        t[0] = 0  # the padding row
+        tables[f['name']] = t
+    return dict(tables=tables, dcat=dcat, W=rnd(64, dcat, seed=50) * 0.2, b=0.1 * rnd(64, seed=51),
+                pos=rnd(L, 64, seed=52) * 0.5, Win=rnd(192, 64, seed=53) * 0.15, bin=0.1 * rnd(192, seed=54),
+                key=torch.tensor([4321, 7], dtype=torch.int64, device=DEV))
+
+
+def _modules(w):
+    lin = types.SimpleNamespace(weight=w['W'], bias=w['b'])
+    attn = types.SimpleNamespace(in_proj_weight=w['Win'], in_proj_bias=w['bin'], embed_dim=64, num_heads=4)
+    return lin, attn
+
+
+def _separate(segs, M, w, p, err=None, cat=None):
+    """The three kernels the head replaces -> (x0, cat, qkv0)."""
+    if cat is None:
+        cat = ops.gather_fwd(segs, M, torch.empty(M, w['dcat'], device=DEV), err)
+    x0 = ops.linear_fwd(cat, w['W'], w['b'], aux=w['pos'], aux_mod=L, drop_p=p, drop_key=w['key'] if p > 0 else None,
+                        site_a=0, site_b=1)
+    qkv = ops.linear_fwd(x0, w['Win'], w['bin'], out_dtype=torch.bfloat16)
+    return x0, cat, qkv
+
+
+def _head(segs, M, w, p, err=None):
+    return ops.seq_head_fwd(segs, M, L, w['dcat'], w['W'], w['b'], w['pos'], w['Win'], w['bin'], err, p,
+                            w['key'] if p > 0 else None, 0, 1)
+
+
+_CASE = {}
+
+
+def _case(kind, B):
+    """Inputs and the gathered fp32 cat of one (schema, batch), built once."""
+    if (kind, B) not in _CASE:
+        feats = _features(kind)
+        w = _weights(feats)
+        ids = _ids(feats, B)
+        segs, dcat = _segments(feats, ids, w['tables'])
+        assert dcat == w['dcat']
+        cat = ops.gather_fwd(segs, B * L, torch.empty(B * L, dcat, device=DEV))
+        _CASE[(kind, B)] = (feats, w, ids, segs, cat)
+    return _CASE[(kind, B)]
+
+
+@pytest.mark.parametrize('p', [0.0, 0.15])
+@pytest.mark.parametrize('B', BATCHES)
+@pytest.mark.parametrize('kind', KINDS)
+def test_head_bitwise_against_separate_kernels(kind, B, p, bf16_mode):
+    feats, w, ids, segs, cat = _case(kind, B)
+    M = B * L
+    lin, attn = _modules(w)
+    assert ops.seq_head_ok(segs, M, L, w['dcat'], lin, w['pos'], attn)
+    x0r, _, qkvr = _separate(segs, M, w, p, cat=cat)
+    assert qkvr.dtype == torch.bfloat16
+    x0, cat_h, qkv = _head(segs, M, w, p)
+    torch.cuda.synchronize()
+    assert cat_h.dtype == torch.float32 and tuple(cat_h.shape) == (M, w['dcat'])
+    assert torch.equal(cat_h, cat), (cat_h - cat).abs().max().item()
+    assert torch.equal(cat_h.to(torch.bfloat16), cat.to(torch.bfloat16))  # the operand of the product
+    assert torch.equal(x0, x0r), (x0 - x0r).abs().max().item()
+    assert torch.equal(qkv, qkvr), (qkv.float() - qkvr.float()).abs().max().item()
+    assert x0.abs().max().item() > 0 and (p == 0 or (x0 == 0).any())
+    if p == 0:
+        # and the pair agrees with torch: exact products of the bf16-rounded operands, so only the
+        # fp32 summation order of at most 64 terms differs (the bound of test_gpu_linear_bwd's dcat)
+        r16 = lambda t: t.to(torch.bfloat16).double()  # noqa: E731
+        ref = r16(cat) @ r16(w['W']).t() + w['b'].double() + w['pos'].double().repeat(B, 1)
+        err, scale = (x0.double() - ref).abs().max().item(), ref.abs().max().item()
+        print('x0 err', err, 'scale', scale)
+        assert err < 2e-5 * scale, (err, scale)
+
+
+def test_head_bad_ids(bf16_mode):
+    """One id = vocab (the id feature) and one id = -1 (a tag list whose other tags are padding):
+    zeros in those rows' columns, the error flag raised, every other row unchanged; the separate
+    kernels behave the same."""
+    feats = _features('c2')
+    w = _weights(feats)
+    B = BATCHES[0]
+    M = B * L
+    ids = _ids(feats, B, seed=5)
+    good = {k: v.clone() for k, v in ids.items()}
+    ra, rb = 1234, 30001
+    ids['hist_movie_ids'].view(-1)[ra] = 97
+    ids['hist_genre_ids'].view(M, 3)[rb] = torch.tensor([0, -1, 0], device=DEV)
+    segs, _ = _segments(feats, ids, w['tables'])
+    errs = [torch.zeros(1, dtype=torch.int32, device=DEV) for _ in range(2)]
+    x0r, catr, qkvr = _separate(segs, M, w, 0.15, err=errs[0])
+    x0, cat_h, qkv = _head(segs, M, w, 0.15, err=errs[1])
+    torch.cuda.synchronize()
+    assert errs[0].item() == 1 and errs[1].item() == 1
+    assert torch.count_nonzero(cat_h[ra, :32]) == 0 and torch.count_nonzero(cat_h[rb, 32:]) == 0
+    assert torch.count_nonzero(catr[ra, :32]) == 0 and torch.count_nonzero(catr[rb, 32:]) == 0
+    assert torch.equal(cat_h, catr) and torch.equal(x0, x0r) and torch.equal(qkv, qkvr)
+    # the other rows are those of the clean ids, and clean ids leave the flag alone
+    gsegs, _ = _segments(feats, good, w['tables'])
+    err = torch.zeros(1, dtype=torch.int32, device=DEV)
+    x0g, cat_g, qkvg = _head(gsegs, M, w, 0.15, err=err)
+    torch.cuda.synchronize()
+    assert err.item() == 0
+    keep = torch.ones(M, dtype=torch.bool, device=DEV)
+    keep[ra] = keep[rb] = False
+    assert torch.equal(x0[keep], x0g[keep]) and torch.equal(qkv[keep], qkvg[keep])
+    assert torch.equal(cat_h[keep], cat_g[keep])
+
+
+def _encoder(feats, n_layers=2, dropout=0.1, seed=11):
+    from recommendsystemproject_amd.project.models.TwoTower.SequenceEncoder import SequenceEncoder
+    torch.manual_seed(seed)
+    enc = SequenceEncoder(feats, model_dim=64, dim_feedforward=256, max_seq_len=L, n_head=4, n_layers=n_layers,
+                          dropout=dropout)
+    return enc.to(DEV).train()
+
+
+def _run_encoder(enc, ids, monkeypatch, switch, backward=False):
+    """One forward (+ backward) with RSYS_SEQ_HEAD_FUSED = switch (None: unset) from the same dropout
+    streams -> (output, flat gradient or None, calls of the fused head)."""
+    from recommendsystemproject_amd.flat import ensure_flat
+    if switch is None:
+        monkeypatch.delenv('RSYS_SEQ_HEAD_FUSED', raising=False)
+    else:
+        monkeypatch.setenv('RSYS_SEQ_HEAD_FUSED', switch)
+    calls = [0]
+    head = ops.seq_head_fwd
+
+    def spy(*a, **k):
+        calls[0] += 1
+        return head(*a, **k)
+
+    monkeypatch.setattr(ops, 'seq_head_fwd', spy)
+    rng = [(m, m.rng_state.clone()) for m in enc.modules() if isinstance(getattr(m, 'rng_state', None), torch.Tensor)]
+    try:
+        f = ensure_flat(enc)
+        f.zero_grad()
+        out = enc(ids)
+        grad = None
+        if backward:
+            out.backward(rnd(*out.shape, seed=21))
+            torch.cuda.synchronize()
+            grad = f.grad.clone()
+        torch.cuda.synchronize()
+    finally:
+        monkeypatch.setattr(ops, 'seq_head_fwd', head)
+        for m, st in rng:
+            m.rng_state.copy_(st)
+    return out.detach().clone(), grad, calls[0]
+
+
+def test_encoder_step_switch_on_equals_off(monkeypatch):
+    """One SequenceEncoder forward + backward at B = 656 (dropout on, two layers) with the fused head
+    against RSYS_SEQ_HEAD_FUSED=0: output and every parameter gradient bitwise, deterministic mode."""
+    monkeypatch.setenv('RSYS_DETERMINISTIC', '1')
+    feats = _features('c2')
+    enc = _encoder(feats)
+    ids = _ids(feats, BATCHES[0], seed=7)
+    precision.set_compute_dtype('bf16')
+    try:
+        on = _run_encoder(enc, ids, monkeypatch, None, backward=True)
+        off = _run_encoder(enc, ids, monkeypatch, '0', backward=True)
+    finally:
+        precision.set_compute_dtype('fp32')
+    assert on[2] == 1 and off[2] == 0
+    assert on[1].abs().max().item() > 0
+    assert torch.equal(on[0], off[0])
+    assert torch.equal(on[1], off[1]), (on[1] - off[1]).abs().max().item()
+
+
+@pytest.mark.parametrize('why', ['ragged_rows', 'fp32', 'switch_off'])
+def test_fallbacks_run_the_separate_kernels(why, monkeypatch):
+    """M = 32,850 (not a multiple of 16), the fp32 mode and RSYS_SEQ_HEAD_FUSED=0: seq_head_ok is
+    false, the fused head is not called, and the encoder output is the switch-off output."""
+    feats = _features('c2')
+    B = 657 if why == 'ragged_rows' else BATCHES[0]
+    M = B * L
+    enc = _encoder(feats, dropout=0.0)
+    ids = _ids(feats, B, seed=9)
+    precision.set_compute_dtype('fp32' if why == 'fp32' else 'bf16')
+    try:
+        proc = enc.feature_embedder
+        segs, tables, dcat, _ = functions.seq_feature_segments(proc, ids, B, L)
+        args = (segs, M, L, dcat, proc.feature_projection[0], proc.pos_emb.weight,
+                enc.transformer_backbone.layers[0].self_attn)
+        if why == 'switch_off':
+            assert ops.seq_head_ok(*args)
+            monkeypatch.setenv('RSYS_SEQ_HEAD_FUSED', '0')
+        assert not ops.seq_head_ok(*args)
+        got = _run_encoder(enc, ids, monkeypatch, '0' if why == 'switch_off' else None)
+        off = _run_encoder(enc, ids, monkeypatch, '0')
+    finally:
+        precision.set_compute_dtype('fp32')
+    assert got[2] == 0 and off[2] == 0
+    assert torch.equal(got[0], off[0])
+
+
+def test_max_pooling_is_not_taken(bf16_mode):
+    """A max-pooled segment is not the kernel's (SequenceFeatureProcessor itself only accepts mean
+    and sum for tag lists, so no encoder reaches it): seq_head_ok is false and the library refuses
+    the call instead of computing something else; the separate gather takes the segment."""
+    feats, w, ids, segs, _ = _case('c2', BATCHES[0])
+    M = BATCHES[0] * L
+    msegs, _ = _segments(feats, ids, w['tables'])
+    msegs[1].pool_mode = _hip.RS_POOL['max']
+    lin, attn = _modules(w)
+    assert ops.seq_head_ok(segs, M, L, w['dcat'], lin, w['pos'], attn)
+    assert not ops.seq_head_ok(msegs, M, L, w['dcat'], lin, w['pos'], attn)
+    with pytest.raises(_hip.HipError, match='unsupported schema'):
+        _head(msegs, M, w, 0.0)
+    cat = ops.gather_fwd(msegs, M, torch.empty(M, w['dcat'], device=DEV))
+    torch.cuda.synchronize()
+    want = w['tables']['hist_genre_ids'][ids['hist_genre_ids'].view(M, 3)].max(1).values
+    assert torch.equal(cat[:, 32:], want)
