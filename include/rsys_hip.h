@@ -646,6 +646,35 @@ int rs_target_rank(const float* U, int64_t ldu, int B, const void* items, int it
                    const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
                    const int32_t* hist_idx, int64_t num_users, int splits, void* ws, int64_t ws_bytes,
                    int32_t* out_rank, void* stream);
+/* The same two over an OCP e4m3 (fn: no inf, max 448; torch.float8_e4m3fn) item index: rows
+ * [N, D] bytes, row stride ldi in BYTES (a multiple of 16), row c = RNE(x[c] * 2^item_exp) under
+ * ONE power-of-two scale for the index. rs_e4m3_exponent(absmax) is that exponent: the largest e
+ * with absmax * 2^e <= 448, clamped to [-40, 40], 0 for absmax = 0, taken from the float's
+ * exponent and mantissa bits (host and device agree exactly). Users are quantised inside the
+ * kernel, each row under its own exponent e_u by the same rule, with the hardware's RNE
+ * conversion; scores are acc * 2^-(e_u + item_exp) (exact), acc the fp32 sum of the products of
+ * the quantised values (every e4m3 value is a bf16 value: the bytes go to the bf16 MFMA, whose
+ * accumulation is the bf16 path's). Embeddings must be finite. Every other
+ * argument, check and message, the splits and the workspace as rs_fused_topk / rs_target_rank.
+ * rs_e4m3_encode_host: out[i] = the e4m3 byte of x[i] * 2^exp, a software RNE encoder (ties to the
+ * even code, subnormals in steps of 2^-9, the sign of zero kept; anything that rounds past 448, inf
+ * and NaN -> 0x7f | sign): the definition rs_quantize_e4m3 is held to. rs_quantize_e4m3: the same
+ * on the device, fp32 rows [N, D] (stride ldx floats) to byte rows (stride ldq bytes, a multiple
+ * of 16), D a multiple of 16, any N. */
+int rs_e4m3_exponent(float absmax);                                           /* host only */
+int rs_e4m3_encode_host(const float* x, int64_t n, int exp, uint8_t* out);    /* host only */
+int rs_quantize_e4m3(const float* x, int64_t ldx, int64_t N, int D, int exp, uint8_t* q, int64_t ldq,
+                     void* stream);
+int rs_fused_topk_e4m3(const float* U, int64_t ldu, int B, const void* items, int item_exp, int64_t ldi,
+                       int64_t N, int D, int K, const int64_t* user_ids, int64_t uid_stride,
+                       const int64_t* hist_off, const int32_t* hist_idx, int64_t num_users, int splits,
+                       void* ws, int64_t ws_bytes, int32_t* out_idx, float* out_val, int64_t ld_out,
+                       void* stream);
+int rs_target_rank_e4m3(const float* U, int64_t ldu, int B, const void* items, int item_exp, int64_t ldi,
+                        int64_t N, int D, const int32_t* target_col, int64_t tc_stride,
+                        const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
+                        const int32_t* hist_idx, int64_t num_users, int splits, void* ws, int64_t ws_bytes,
+                        int32_t* out_rank, void* stream);
 
 /* ---------------------------------------------------------------- clip + Adam
  * Flat multi-tensor path over a contiguous fp32 range (all parameters packed in one buffer).

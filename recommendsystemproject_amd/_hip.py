@@ -164,6 +164,13 @@ SIGNATURES = {
     'rs_target_rank_ws_bytes': (i64, [i32, i64, i32, i32]),
     'rs_target_rank': (i32, [vp, i64, i32, vp, i32, i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, i32, vp, i64, vp,
                              vp]),
+    'rs_e4m3_exponent': (i32, [f32]),
+    'rs_e4m3_encode_host': (i32, [vp, i64, i32, vp]),
+    'rs_quantize_e4m3': (i32, [vp, i64, i64, i32, i32, vp, i64, vp]),
+    'rs_fused_topk_e4m3': (i32, [vp, i64, i32, vp, i32, i64, i64, i32, i32, vp, i64, vp, vp, i64, i32, vp, i64,
+                                 vp, vp, i64, vp]),
+    'rs_target_rank_e4m3': (i32, [vp, i64, i32, vp, i32, i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, i32, vp,
+                                  i64, vp, vp]),
     'rs_collate_ragged': (i32, [vp, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
     'rs_catalog_gather': (i32, [vp, i32, i32, i64, i32, i64, vp, i32, i32, i64, vp, i64, vp, vp]),
     'rs_sqnorm_ws_bytes': (i64, [i64]),

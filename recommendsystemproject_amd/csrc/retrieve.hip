@@ -47,6 +47,7 @@ struct FtArgs {
   const void* items;
   int64_t ldi;
   int N, D, K;
+  int item_exp;  // e4m3 items: the index's scale exponent
   const int64_t* user_ids;
   int64_t uid_stride;
   const int64_t* hist_off;
@@ -93,10 +94,10 @@ __device__ __forceinline__ void ft_prune_row(unsigned long long* L, int* cnt, fl
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
-template <int DP, bool F32, int KB>
-__global__ __launch_bounds__((FtCfg<DP, F32, KB>::NT)) void fused_topk_kernel(FtArgs a) {
-  using Cfg = FtCfg<DP, F32, KB>;
-  using E = std::conditional_t<F32, float, __bf16>;
+template <int DP, FtElem EK, int KB>
+__global__ __launch_bounds__((FtCfg<DP, EK, KB>::NT)) void fused_topk_kernel(FtArgs a) {
+  using Cfg = FtCfg<DP, EK, KB>;
+  using E = FtStore<EK>;
   constexpr int ROWS = Cfg::ROWS, CAP = Cfg::CAP, TI = Cfg::TI, NB = Cfg::NB;
   constexpr int SL = Cfg::SL, ESZ = Cfg::ESZ;
   __shared__ __attribute__((aligned(16))) E tiles[2][TI * Cfg::PTMAX];
@@ -108,7 +109,7 @@ __global__ __launch_bounds__((FtCfg<DP, F32, KB>::NT)) void fused_topk_kernel(Ft
   const int c = lane & 31, h = lane >> 5;
   const int rt = blockIdx.x % a.nrt, split = blockIdx.x / a.nrt;
   const int D = a.D, K = a.K;
-  const int PT = F32 ? D + 4 : D + 8;
+  const int PT = ft_pitch<EK>(D);
   const int lrow = wave * 32 + c;  // this lane's user: list row and, + rt * ROWS, batch row
   const int o = rt * ROWS + lrow;
   const bool o_ok = o < a.B;
@@ -133,8 +134,8 @@ __global__ __launch_bounds__((FtCfg<DP, F32, KB>::NT)) void fused_topk_kernel(Ft
     }
   }
 
-  FtUser<DP, F32> uf;  // user fragments (B operand)
-  uf.load(a.U, a.ldu, o, o_ok, D, h);
+  FtUser<DP, EK> uf;  // user fragments (B operand)
+  uf.load(a.U, a.ldu, o, o_ok, D, h, a.item_exp);
 
   // staging registers of the tiles in flight (retrieve_tile.h)
   constexpr int DEPTH = Cfg::DEPTH;
@@ -182,7 +183,7 @@ __global__ __launch_bounds__((FtCfg<DP, F32, KB>::NT)) void fused_topk_kernel(Ft
 
   auto compute_tile = [&](int t) {
     floatx16 acc[NB];
-    ft_mfma<DP, F32, NB>(tiles[t & 1], PT, D, c, h, uf, acc);
+    ft_mfma<DP, EK, NB>(tiles[t & 1], PT, D, c, h, uf, acc);
 #pragma unroll
     for (int ib = 0; ib < NB; ++ib) {
       float m = acc[ib][0];
@@ -231,7 +232,8 @@ __global__ __launch_bounds__((FtCfg<DP, F32, KB>::NT)) void fused_topk_kernel(Ft
 // Target rank (rs_target_rank): for every user the number of catalog columns that precede its
 // target column in rs_fused_topk's order (masked value descending, ties by the lower column); a
 // full-catalog rank without candidate lists, prunes or a K. Same grid, staging and MFMA tiles as
-// the four-wave fused_topk_kernel; only the two item tiles live in LDS.
+// the four-wave fused_topk_kernel; only the two item tiles live in LDS. Item rows are fp32, bf16
+// or e4m3 bytes under one scale (retrieve_tile.h FtElem; rs_*_e4m3), one instance each.
 //
 // The target's score is formed by the same MFMA sequence as every other score, so that exact
 // copies of the target row tie with it: before the sweep a wave stages the target rows of its 32
@@ -257,6 +259,7 @@ struct TrArgs {
   const void* items;
   int64_t ldi;
   int N, D;
+  int item_exp;  // e4m3 items: the index's scale exponent
   const int32_t* target_col;
   int64_t tc_stride;
   const int64_t* user_ids;
@@ -268,10 +271,10 @@ struct TrArgs {
   int32_t* out;  // one split: the ranks [B]; else this split's partial counts at split * B
 };
 
-template <int DP, bool F32>
-__global__ __launch_bounds__((FtCfg<DP, F32, 0>::NT)) void target_rank_kernel(TrArgs a) {
-  using Cfg = FtCfg<DP, F32, 0>;
-  using E = std::conditional_t<F32, float, __bf16>;
+template <int DP, FtElem EK>
+__global__ __launch_bounds__((FtCfg<DP, EK, 0>::NT)) void target_rank_kernel(TrArgs a) {
+  using Cfg = FtCfg<DP, EK, 0>;
+  using E = FtStore<EK>;
   constexpr int NW = Cfg::NW, ROWS = Cfg::ROWS, TI = Cfg::TI, NB = Cfg::NB, SL = Cfg::SL, ESZ = Cfg::ESZ;
   __shared__ __attribute__((aligned(16))) E tiles[2][TI * Cfg::PTMAX];
 
@@ -279,7 +282,7 @@ __global__ __launch_bounds__((FtCfg<DP, F32, 0>::NT)) void target_rank_kernel(Tr
   const int c = lane & 31, h = lane >> 5;
   const int rt = blockIdx.x % a.nrt, split = blockIdx.x / a.nrt;
   const int D = a.D;
-  const int PT = F32 ? D + 4 : D + 8;
+  const int PT = ft_pitch<EK>(D);
   const int o = rt * ROWS + wave * 32 + c;  // this lane's user
   const bool o_ok = o < a.B;
   const int c_begin = split * a.split_cols;
@@ -300,8 +303,8 @@ __global__ __launch_bounds__((FtCfg<DP, F32, 0>::NT)) void target_rank_kernel(Tr
     }
   }
 
-  FtUser<DP, F32> uf;  // user fragments (B operand)
-  uf.load(a.U, a.ldu, o, o_ok, D, h);
+  FtUser<DP, EK> uf;  // user fragments (B operand)
+  uf.load(a.U, a.ldu, o, o_ok, D, h, a.item_exp);
 
   constexpr int DEPTH = Cfg::DEPTH;
   u32x4 st[DEPTH][SL];
@@ -321,17 +324,18 @@ __global__ __launch_bounds__((FtCfg<DP, F32, 0>::NT)) void target_rank_kernel(Tr
     for (int w0 = 0; w0 < NW; w0 += WPR) {
       const bool mine = wave >= w0 && wave < w0 + WPR;
       if (mine) {
-        for (int slot = lane; slot < 32 * cpr; slot += 64) {  // 32 cpr is a multiple of 64
+        for (int slot = lane; slot < 32 * cpr; slot += 64) {  // rows < 32: always an active source lane
           const int row = slot / cpr, ch = slot % cpr;
           const int64_t g = __shfl(max(tcol, 0), row);
-          *reinterpret_cast<u32x4*>(reinterpret_cast<char*>(blk) + row * PT * ESZ + ch * 16) =
-              *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(a.items) + g * a.ldi * ESZ + ch * 16);
+          ft_store_slot<ESZ>(blk, PT, row, ch,
+                             *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(a.items) +
+                                                             g * a.ldi * ESZ + ch * 16));
         }
       }
       __syncthreads();
       if (mine) {
         floatx16 acc[1];
-        ft_mfma<DP, F32, 1>(blk, PT, D, c, h, uf, acc);
+        ft_mfma<DP, EK, 1>(blk, PT, D, c, h, uf, acc);
         // item row c of the block is element 4 (c >> 3) + (c & 3) of the half-lane (c >> 2) & 1
         const int ed = 4 * (c >> 3) + (c & 3);
         float v = 0.f;
@@ -405,7 +409,7 @@ __global__ __launch_bounds__((FtCfg<DP, F32, 0>::NT)) void target_rank_kernel(Tr
 
   auto compute_tile = [&](int t) {
     floatx16 acc[NB];
-    ft_mfma<DP, F32, NB>(tiles[t & 1], PT, D, c, h, uf, acc);
+    ft_mfma<DP, EK, NB>(tiles[t & 1], PT, D, c, h, uf, acc);
 #pragma unroll
     for (int ib = 0; ib < NB; ++ib) count_block(acc[ib], c_begin + t * TI + ib * 32);
   };
@@ -471,31 +475,31 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ 
 
 inline int ft_rows(int K) { return K <= kFtSmallK ? 128 : 32; }
 
-template <int DP, bool F32>
+template <int DP, FtElem EK>
 int ft_launch_k(const FtArgs& a, int grid, hipStream_t st) {
   if (a.K <= kFtSmallK)
-    fused_topk_kernel<DP, F32, 0><<<grid, FtCfg<DP, F32, 0>::NT, 0, st>>>(a);
+    fused_topk_kernel<DP, EK, 0><<<grid, FtCfg<DP, EK, 0>::NT, 0, st>>>(a);
   else
-    fused_topk_kernel<DP, F32, 1><<<grid, FtCfg<DP, F32, 1>::NT, 0, st>>>(a);
+    fused_topk_kernel<DP, EK, 1><<<grid, FtCfg<DP, EK, 1>::NT, 0, st>>>(a);
   RS_CHECK_LAUNCH("rs_fused_topk");
   return 0;
 }
 
-template <bool F32>
+template <FtElem EK>
 int ft_launch(const FtArgs& a, int grid, hipStream_t st) {
-  if (a.D <= 64) return ft_launch_k<64, F32>(a, grid, st);
-  if (a.D <= 128) return ft_launch_k<128, F32>(a, grid, st);
-  return ft_launch_k<256, F32>(a, grid, st);
+  if (a.D <= 64) return ft_launch_k<64, EK>(a, grid, st);
+  if (a.D <= 128) return ft_launch_k<128, EK>(a, grid, st);
+  return ft_launch_k<256, EK>(a, grid, st);
 }
 
-template <bool F32>
+template <FtElem EK>
 int tr_launch(const TrArgs& a, int grid, hipStream_t st) {
   if (a.D <= 64)
-    target_rank_kernel<64, F32><<<grid, FtCfg<64, F32, 0>::NT, 0, st>>>(a);
+    target_rank_kernel<64, EK><<<grid, FtCfg<64, EK, 0>::NT, 0, st>>>(a);
   else if (a.D <= 128)
-    target_rank_kernel<128, F32><<<grid, FtCfg<128, F32, 0>::NT, 0, st>>>(a);
+    target_rank_kernel<128, EK><<<grid, FtCfg<128, EK, 0>::NT, 0, st>>>(a);
   else
-    target_rank_kernel<256, F32><<<grid, FtCfg<256, F32, 0>::NT, 0, st>>>(a);
+    target_rank_kernel<256, EK><<<grid, FtCfg<256, EK, 0>::NT, 0, st>>>(a);
   RS_CHECK_LAUNCH("rs_target_rank");
   return 0;
 }
@@ -524,17 +528,19 @@ extern "C" int64_t rs_fused_topk_ws_bytes(int B, int64_t N, int D, int K, int sp
   return (int64_t)B * splits * K * 8;  // values fp32 + columns int32, [B][splits * K] each
 }
 
-extern "C" int rs_fused_topk(const float* U, int64_t ldu, int B, const void* items, int items_bf16,
-                             int64_t ldi, int64_t N, int D, int K, const int64_t* user_ids,
-                             int64_t uid_stride, const int64_t* hist_off, const int32_t* hist_idx,
-                             int64_t num_users, int splits, void* ws, int64_t ws_bytes, int32_t* out_idx,
-                             float* out_val, int64_t ld_out, void* stream) {
+// rs_fused_topk and rs_fused_topk_e4m3: ek the item element, ldi in elements (e4m3: bytes)
+static int fused_topk_any(const float* U, int64_t ldu, int B, const void* items, FtElem ek, int item_exp,
+                          int64_t ldi, int64_t N, int D, int K, const int64_t* user_ids, int64_t uid_stride,
+                          const int64_t* hist_off, const int32_t* hist_idx, int64_t num_users, int splits,
+                          void* ws, int64_t ws_bytes, int32_t* out_idx, float* out_val, int64_t ld_out,
+                          void* stream) {
+  const int ld_mult = ek == kF32 ? 4 : ek == kBF16 ? 8 : 16;  // a row stride of whole 16-byte chunks
   RS_CHECK_ARG(U && items && out_idx && B >= 0, "rs_fused_topk: null U / items / out_idx or B < 0");
   RS_CHECK_ARG(D >= 16 && D <= 256 && D % 16 == 0,
                "rs_fused_topk: D = %d, must be a multiple of 16 in [16, 256]", D);
   RS_CHECK_ARG(K >= 1 && K <= kFtMaxK && N >= 1 && N < (int64_t)1 << 31 && K <= N,
                "rs_fused_topk: bad sizes (N=%lld K=%d; K <= min(N, 256), N < 2^31)", (long long)N, K);
-  RS_CHECK_ARG(ldu >= D && ldu % 4 == 0 && ldi >= D && ldi % (items_bf16 ? 8 : 4) == 0 && aligned16(U) &&
+  RS_CHECK_ARG(ldu >= D && ldu % 4 == 0 && ldi >= D && ldi % ld_mult == 0 && aligned16(U) &&
                    aligned16(items) && ld_out >= K,
                "rs_fused_topk: rows of U and items must be 16-byte aligned, ld >= D, ld_out >= K");
   if (splits <= 0) splits = rs_fused_topk_splits(B, N, D, K);
@@ -547,7 +553,7 @@ extern "C" int rs_fused_topk(const float* U, int64_t ldu, int B, const void* ite
   if (B == 0) return 0;
   FtArgs a;
   a.U = U; a.ldu = ldu; a.B = B;
-  a.items = items; a.ldi = ldi; a.N = (int)N; a.D = D; a.K = K;
+  a.items = items; a.ldi = ldi; a.N = (int)N; a.D = D; a.K = K; a.item_exp = item_exp;
   a.user_ids = user_ids; a.uid_stride = uid_stride; a.hist_off = hist_off; a.hist_idx = hist_idx;
   a.num_users = num_users;
   a.splits = splits; a.split_cols = (int)(N / splits); a.nrt = cdiv(B, ft_rows(K));
@@ -561,11 +567,32 @@ extern "C" int rs_fused_topk(const float* U, int64_t ldu, int B, const void* ite
   }
   const int64_t grid = (int64_t)a.nrt * splits;
   RS_CHECK_ARG(grid < (int64_t)1 << 31, "rs_fused_topk: grid too large");
-  RS_RET_IF(items_bf16 ? ft_launch<false>(a, (int)grid, as_stream(stream))
-                       : ft_launch<true>(a, (int)grid, as_stream(stream)));
+  RS_RET_IF(ek == kF32    ? ft_launch<kF32>(a, (int)grid, as_stream(stream))
+            : ek == kBF16 ? ft_launch<kBF16>(a, (int)grid, as_stream(stream))
+                          : ft_launch<kE4M3>(a, (int)grid, as_stream(stream)));
   if (splits == 1) return 0;
   // split-major candidates, sorted within a split: position order == column order among equal values
   return rs_topk_rows(ws_val, ldw, B, (int)ldw, K, ws_idx, ldw, 0, out_idx, out_val, ld_out, stream);
+}
+
+extern "C" int rs_fused_topk(const float* U, int64_t ldu, int B, const void* items, int items_bf16,
+                             int64_t ldi, int64_t N, int D, int K, const int64_t* user_ids,
+                             int64_t uid_stride, const int64_t* hist_off, const int32_t* hist_idx,
+                             int64_t num_users, int splits, void* ws, int64_t ws_bytes, int32_t* out_idx,
+                             float* out_val, int64_t ld_out, void* stream) {
+  return fused_topk_any(U, ldu, B, items, items_bf16 ? kBF16 : kF32, 0, ldi, N, D, K, user_ids, uid_stride,
+                        hist_off, hist_idx, num_users, splits, ws, ws_bytes, out_idx, out_val, ld_out, stream);
+}
+
+extern "C" int rs_fused_topk_e4m3(const float* U, int64_t ldu, int B, const void* items, int item_exp,
+                                  int64_t ldi, int64_t N, int D, int K, const int64_t* user_ids,
+                                  int64_t uid_stride, const int64_t* hist_off, const int32_t* hist_idx,
+                                  int64_t num_users, int splits, void* ws, int64_t ws_bytes,
+                                  int32_t* out_idx, float* out_val, int64_t ld_out, void* stream) {
+  RS_CHECK_ARG(item_exp >= -kE4m3MaxExp && item_exp <= kE4m3MaxExp,
+               "rs_fused_topk_e4m3: item_exp = %d outside [-40, 40]", item_exp);
+  return fused_topk_any(U, ldu, B, items, kE4M3, item_exp, ldi, N, D, K, user_ids, uid_stride, hist_off,
+                        hist_idx, num_users, splits, ws, ws_bytes, out_idx, out_val, ld_out, stream);
 }
 
 extern "C" int rs_target_rank_splits(int B, int64_t N, int D) {
@@ -587,17 +614,19 @@ extern "C" int64_t rs_target_rank_ws_bytes(int B, int64_t N, int D, int splits) 
   return n < 16 ? 16 : n;
 }
 
-extern "C" int rs_target_rank(const float* U, int64_t ldu, int B, const void* items, int items_bf16,
-                              int64_t ldi, int64_t N, int D, const int32_t* target_col, int64_t tc_stride,
-                              const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
-                              const int32_t* hist_idx, int64_t num_users, int splits, void* ws,
-                              int64_t ws_bytes, int32_t* out_rank, void* stream) {
+// rs_target_rank and rs_target_rank_e4m3: ek the item element, ldi in elements (e4m3: bytes)
+static int target_rank_any(const float* U, int64_t ldu, int B, const void* items, FtElem ek, int item_exp,
+                           int64_t ldi, int64_t N, int D, const int32_t* target_col, int64_t tc_stride,
+                           const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
+                           const int32_t* hist_idx, int64_t num_users, int splits, void* ws, int64_t ws_bytes,
+                           int32_t* out_rank, void* stream) {
+  const int ld_mult = ek == kF32 ? 4 : ek == kBF16 ? 8 : 16;  // a row stride of whole 16-byte chunks
   RS_CHECK_ARG(U && items && target_col && out_rank && B >= 0,
                "rs_target_rank: null U / items / target_col / out_rank or B < 0");
   RS_CHECK_ARG(D >= 16 && D <= 256 && D % 16 == 0,
                "rs_target_rank: D = %d, must be a multiple of 16 in [16, 256]", D);
   RS_CHECK_ARG(N >= 1 && N < (int64_t)1 << 31, "rs_target_rank: bad sizes (N=%lld; 1 <= N < 2^31)", (long long)N);
-  RS_CHECK_ARG(ldu >= D && ldu % 4 == 0 && ldi >= D && ldi % (items_bf16 ? 8 : 4) == 0 && aligned16(U) &&
+  RS_CHECK_ARG(ldu >= D && ldu % 4 == 0 && ldi >= D && ldi % ld_mult == 0 && aligned16(U) &&
                    aligned16(items),
                "rs_target_rank: rows of U and items must be 16-byte aligned, ld >= D");
   if (splits <= 0) splits = rs_target_rank_splits(B, N, D);
@@ -609,7 +638,7 @@ extern "C" int rs_target_rank(const float* U, int64_t ldu, int B, const void* it
   if (B == 0) return 0;
   TrArgs a;
   a.U = U; a.ldu = ldu; a.B = B;
-  a.items = items; a.ldi = ldi; a.N = (int)N; a.D = D;
+  a.items = items; a.ldi = ldi; a.N = (int)N; a.D = D; a.item_exp = item_exp;
   a.target_col = target_col; a.tc_stride = tc_stride;
   a.user_ids = user_ids; a.uid_stride = uid_stride; a.hist_off = hist_off; a.hist_idx = hist_idx;
   a.num_users = num_users;
@@ -617,12 +646,84 @@ extern "C" int rs_target_rank(const float* U, int64_t ldu, int B, const void* it
   a.out = splits == 1 ? out_rank : static_cast<int32_t*>(ws);
   const int64_t grid = (int64_t)a.nrt * splits;
   RS_CHECK_ARG(grid < (int64_t)1 << 31, "rs_target_rank: grid too large");
-  RS_RET_IF(items_bf16 ? tr_launch<false>(a, (int)grid, as_stream(stream))
-                       : tr_launch<true>(a, (int)grid, as_stream(stream)));
+  RS_RET_IF(ek == kF32    ? tr_launch<kF32>(a, (int)grid, as_stream(stream))
+            : ek == kBF16 ? tr_launch<kBF16>(a, (int)grid, as_stream(stream))
+                          : tr_launch<kE4M3>(a, (int)grid, as_stream(stream)));
   if (splits == 1) return 0;
   target_rank_reduce<<<cdiv(B, 256), 256, 0, as_stream(stream)>>>(a.out, splits, B, target_col, tc_stride, (int)N,
                                                                  out_rank);
   RS_CHECK_LAUNCH("rs_target_rank (reduce)");
+  return 0;
+}
+
+extern "C" int rs_target_rank(const float* U, int64_t ldu, int B, const void* items, int items_bf16,
+                              int64_t ldi, int64_t N, int D, const int32_t* target_col, int64_t tc_stride,
+                              const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
+                              const int32_t* hist_idx, int64_t num_users, int splits, void* ws,
+                              int64_t ws_bytes, int32_t* out_rank, void* stream) {
+  return target_rank_any(U, ldu, B, items, items_bf16 ? kBF16 : kF32, 0, ldi, N, D, target_col, tc_stride,
+                         user_ids, uid_stride, hist_off, hist_idx, num_users, splits, ws, ws_bytes, out_rank,
+                         stream);
+}
+
+extern "C" int rs_target_rank_e4m3(const float* U, int64_t ldu, int B, const void* items, int item_exp,
+                                   int64_t ldi, int64_t N, int D, const int32_t* target_col, int64_t tc_stride,
+                                   const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
+                                   const int32_t* hist_idx, int64_t num_users, int splits, void* ws,
+                                   int64_t ws_bytes, int32_t* out_rank, void* stream) {
+  RS_CHECK_ARG(item_exp >= -kE4m3MaxExp && item_exp <= kE4m3MaxExp,
+               "rs_target_rank_e4m3: item_exp = %d outside [-40, 40]", item_exp);
+  return target_rank_any(U, ldu, B, items, kE4M3, item_exp, ldi, N, D, target_col, tc_stride, user_ids,
+                         uid_stride, hist_off, hist_idx, num_users, splits, ws, ws_bytes, out_rank, stream);
+}
+
+// ---- the e4m3 index format (e4m3.h): scale exponent, host encoder, device quantiser
+
+namespace {
+// one 16-byte chunk of a destination row a thread: 16 floats in, one 16-byte store
+__global__ __launch_bounds__(256) void quantize_e4m3_kernel(const float* __restrict__ x, int64_t ldx, int64_t N,
+                                                            int D, int exp, uint8_t* __restrict__ q,
+                                                            int64_t ldq) {
+  const int cpr = D / 16;  // 16-byte chunks of a destination row
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= N * cpr) return;
+  const int64_t row = i / cpr;
+  const int ch = (int)(i % cpr);
+  const float sc = e4m3_pow2(exp);
+  const float* p = x + row * ldx + 16 * ch;
+  u32x4 w;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) w[j] = e4m3_pack4(ld4(p + 4 * j) * sc);
+  *reinterpret_cast<u32x4*>(q + row * ldq + 16 * ch) = w;
+}
+}  // namespace
+
+extern "C" int rs_e4m3_exponent(float absmax) {
+  uint32_t b;
+  memcpy(&b, &absmax, 4);
+  return e4m3_exponent_bits(b);
+}
+
+extern "C" int rs_e4m3_encode_host(const float* x, int64_t n, int exp, uint8_t* out) {
+  RS_CHECK_ARG((x && out) || n == 0, "rs_e4m3_encode_host: null x / out");
+  RS_CHECK_ARG(n >= 0 && exp >= -kE4m3MaxExp && exp <= kE4m3MaxExp,
+               "rs_e4m3_encode_host: n = %lld < 0 or exp = %d outside [-40, 40]", (long long)n, exp);
+  for (int64_t i = 0; i < n; ++i) out[i] = e4m3_encode_one(ldexpf(x[i], exp));
+  return 0;
+}
+
+extern "C" int rs_quantize_e4m3(const float* x, int64_t ldx, int64_t N, int D, int exp, uint8_t* q, int64_t ldq,
+                                void* stream) {
+  RS_CHECK_ARG(x && q && N >= 0, "rs_quantize_e4m3: null x / q or N < 0");
+  RS_CHECK_ARG(D >= 16 && D % 16 == 0, "rs_quantize_e4m3: D = %d, must be a positive multiple of 16", D);
+  RS_CHECK_ARG(exp >= -kE4m3MaxExp && exp <= kE4m3MaxExp, "rs_quantize_e4m3: exp = %d outside [-40, 40]", exp);
+  RS_CHECK_ARG(ldx >= D && ldx % 4 == 0 && ldq >= D && ldq % 16 == 0 && aligned16(x) && aligned16(q),
+               "rs_quantize_e4m3: rows of x and q must be 16-byte aligned, ld >= D");
+  if (N == 0) return 0;
+  const int64_t blocks = (N * (D / 16) + 255) / 256;
+  RS_CHECK_ARG(blocks < (int64_t)1 << 31, "rs_quantize_e4m3: too many rows");
+  quantize_e4m3_kernel<<<(int)blocks, 256, 0, as_stream(stream)>>>(x, ldx, N, D, exp, q, ldq);
+  RS_CHECK_LAUNCH("rs_quantize_e4m3");
   return 0;
 }
 

@@ -687,17 +687,54 @@ def l2norm_bwd(y, norm, dy, eps=1e-12):
     return dx
 
 
-def fused_topk(U, items, K, user_ids=None, history=None, splits=0):
+def _item_kind(name, items, item_exp):
+    """The entry-point suffix and the dtype argument of fused_topk / target_rank's items."""
+    if items.dtype == torch.float8_e4m3fn:
+        if item_exp is None:
+            raise ValueError(f'{name}: float8_e4m3fn items need item_exp, the index scale exponent (quantize_e4m3)')
+        return '_e4m3', int(item_exp)
+    if items.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'{name}: items must be float32, bfloat16 or float8_e4m3fn, got {items.dtype}')
+    if item_exp is not None:
+        raise ValueError(f'{name}: item_exp goes with float8_e4m3fn items, got {items.dtype}')
+    return '', int(items.dtype == torch.bfloat16)
+
+
+def e4m3_exponent(absmax):
+    """The scale exponent of the e4m3 index format for a largest magnitude (rs_e4m3_exponent): the
+    largest e with absmax * 2^e <= 448, clamped to [-40, 40]; 0 for absmax = 0."""
+    return int(_hip.lib().rs_e4m3_exponent(float(absmax)))
+
+
+def quantize_e4m3(rows, exp=None):
+    """fp32 rows [N, D] (D a multiple of 16) -> (q float8_e4m3fn [N, D], exp): q = RNE(rows * 2^exp)
+    on the device (rs_quantize_e4m3), exp = e4m3_exponent(rows.abs().max()) unless given (one host
+    sync). The rows must be finite."""
+    _hip.require_device(rows)
+    x = rows.detach().float()
+    if x.dim() != 2 or x.shape[1] % 16 or x.shape[1] < 16:
+        raise ValueError(f'quantize_e4m3: rows [N, D] with D a multiple of 16, got {tuple(x.shape)}')
+    if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
+        x = x.contiguous()
+    N, D = int(x.shape[0]), int(x.shape[1])
+    if exp is None:
+        exp = e4m3_exponent(x.abs().max().item()) if N else 0
+    q = torch.empty(N, D, device=x.device, dtype=torch.float8_e4m3fn)
+    call('rs_quantize_e4m3', P(x), int(x.stride(0)), N, D, int(exp), P(q), D, stream())
+    return q, int(exp)
+
+
+def fused_topk(U, items, K, user_ids=None, history=None, splits=0, item_exp=None):
     """The K best catalog columns of every user by dot product, and their scores, without the
-    [B, N] score matrix (rs_fused_topk). U [B, D] fp32; items [N, D] fp32 or bf16 (the dtype picks
-    the kernel); history = (off, idx, num_users) with each user's columns SORTED ascending
+    [B, N] score matrix (rs_fused_topk). U [B, D] fp32; items [N, D] fp32, bf16 or float8_e4m3fn
+    with item_exp, the index scale exponent (the dtype picks the kernel; rs_fused_topk_e4m3);
+    history = (off, idx, num_users) with each user's columns SORTED ascending
     (retrieval.sorted_history_csr), applied when user_ids is given. -> (idx int32 [B, K],
     val fp32 [B, K]), values descending, ties by the lower column. No CPU fallback."""
     use_hist = history is not None and user_ids is not None
     for t in (U, items) + ((user_ids,) + tuple(history[:2]) if use_hist else ()):
         _hip.require_device(t)
-    if items.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f'fused_topk: items must be float32 or bfloat16, got {items.dtype}')
+    suffix, kind = _item_kind('fused_topk', items, item_exp)
     U = U.float()
     if U.stride(1) != 1 or U.stride(0) % 4 or U.data_ptr() % 16:
         U = U.contiguous()
@@ -717,23 +754,22 @@ def fused_topk(U, items, K, user_ids=None, history=None, splits=0):
         uid = user_ids if user_ids.dtype == torch.int64 else user_ids.long()
         us = int(uid.stride(0))
         off, hidx, nu = history
-    call('rs_fused_topk', P(U), int(U.stride(0)), B, P(items), int(items.dtype == torch.bfloat16),
+    call('rs_fused_topk' + suffix, P(U), int(U.stride(0)), B, P(items), kind,
          int(items.stride(0)), N, D, int(K), P(uid), us, P(off), P(hidx), int(nu), int(splits), P(w), int(nbytes),
          P(idx), P(val), K, stream())
     return idx, val
 
 
-def target_rank(U, items, target_cols, user_ids=None, history=None, splits=0):
+def target_rank(U, items, target_cols, user_ids=None, history=None, splits=0, item_exp=None):
     """For every user the 0-based position of catalog column target_cols[b] in fused_topk's order
     over the whole catalog (rs_target_rank): the number of columns with a higher masked score, or
     an equal one and a lower column. rank < K exactly when the target is among the user's top K,
-    for any K. U, items, user_ids and history as fused_topk's (history applies to the target too);
+    for any K. U, items, item_exp, user_ids and history as fused_topk's (history applies to the target too);
     target_cols integer [B], a column outside [0, N) ranks -1. -> int32 [B]. No CPU fallback."""
     use_hist = history is not None and user_ids is not None
     for t in (U, items, target_cols) + ((user_ids,) + tuple(history[:2]) if use_hist else ()):
         _hip.require_device(t)
-    if items.dtype not in (torch.float32, torch.bfloat16):
-        raise TypeError(f'target_rank: items must be float32 or bfloat16, got {items.dtype}')
+    suffix, kind = _item_kind('target_rank', items, item_exp)
     U = U.float()
     if U.stride(1) != 1 or U.stride(0) % 4 or U.data_ptr() % 16:
         U = U.contiguous()
@@ -760,7 +796,7 @@ def target_rank(U, items, target_cols, user_ids=None, history=None, splits=0):
         uid = user_ids if user_ids.dtype == torch.int64 else user_ids.long()
         us = int(uid.stride(0))
         off, hidx, nu = history
-    call('rs_target_rank', P(U), int(U.stride(0)), B, P(items), int(items.dtype == torch.bfloat16),
+    call('rs_target_rank' + suffix, P(U), int(U.stride(0)), B, P(items), kind,
          int(items.stride(0)), N, D, P(tc), int(tc.stride(0)), P(uid), us, P(off), P(hidx), int(nu),
          int(splits), P(w), int(nbytes), P(out), stream())
     return out

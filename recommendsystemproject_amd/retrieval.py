@@ -1,7 +1,7 @@
 """Serving: top-K items for users out of a trained two-tower model.
 
-ItemIndex holds the item tower's embeddings of a catalog (fp32, or bf16 rows at half the memory)
-and answers `search(user_emb, k)` with the fused retrieval kernel (csrc/retrieve.hip: scores are
+ItemIndex holds the item tower's embeddings of a catalog (fp32, bf16 rows at half the memory, or
+OCP e4m3 bytes under one power-of-two scale at a quarter: dtype='fp8') and answers `search(user_emb, k)` with the fused retrieval kernel (csrc/retrieve.hip: scores are
 formed tile by tile on the MFMA and never stored). TwoTowerModel.recommend() runs the user tower
 and searches an index. The result is what validate()'s staged pipeline defines (values descending,
 ties by the lower catalog column, a user's history excluded).
@@ -63,9 +63,11 @@ class ItemIndex:
     """The item embeddings of a catalog, searchable by dot product. Column c of the index is row c
     of the embeddings; `item_ids[c]` is its item id."""
 
-    def __init__(self, rows_fp32, rows_bf16, item_ids, dtype):
+    def __init__(self, rows_fp32, rows_bf16, item_ids, dtype, rows_fp8=None, scale_exp=None):
         self._fp32 = rows_fp32
         self._bf16 = rows_bf16
+        self._fp8 = rows_fp8        # float8_e4m3fn rows: RNE(embedding * 2^scale_exp)
+        self.scale_exp = scale_exp  # None unless dtype == 'fp8'
         self.item_ids = item_ids
         self._dtype = dtype
         self._history = None
@@ -73,17 +75,29 @@ class ItemIndex:
 
     @classmethod
     def from_embeddings(cls, embs, item_ids=None, dtype='fp32', keep_fp32=True):
-        if dtype not in ('fp32', 'bf16'):
-            raise ValueError(f"dtype must be 'fp32' or 'bf16', got {dtype!r}")
+        """dtype 'fp8': e4m3 rows under the scale ops.quantize_e4m3 picks from the largest
+        magnitude (one host sync); finite embeddings of a width the fused kernels take only, as
+        fp8 rows have no staged path."""
+        if dtype not in ('fp32', 'bf16', 'fp8'):
+            raise ValueError(f"dtype must be 'fp32', 'bf16' or 'fp8', got {dtype!r}")
         embs = embs.detach().float().contiguous()
+        if dtype == 'fp8' and (embs.dim() != 2 or not fused_supported(int(embs.shape[1]))):
+            raise ValueError(f'an fp8 index takes embedding widths that are a multiple of 16 in [16, 256], '
+                             f'got {tuple(embs.shape)}')
         if item_ids is None:
             item_ids = torch.arange(embs.shape[0], device=embs.device, dtype=torch.int64)
         item_ids = item_ids.detach().reshape(-1).long().to(embs.device)
         if item_ids.numel() != embs.shape[0]:
             raise ValueError(f'{item_ids.numel()} item ids for {embs.shape[0]} embeddings')
         bf = embs.bfloat16() if dtype == 'bf16' else None
+        q = exp = None
+        if dtype == 'fp8':
+            amax = float(embs.abs().max().item()) if embs.numel() else 0.0
+            if not np.isfinite(amax):
+                raise ValueError('an fp8 index needs finite embeddings (found inf or NaN)')
+            q, exp = ops.quantize_e4m3(embs, ops.e4m3_exponent(amax))
         keep = dtype == 'fp32' or keep_fp32
-        return cls(embs if keep else None, bf, item_ids, dtype)
+        return cls(embs if keep else None, bf, item_ids, dtype, q, exp)
 
     @classmethod
     def build(cls, model, item_loader, device, dtype='fp32', item_id_feature='movie_id_enc',
@@ -118,11 +132,11 @@ class ItemIndex:
 
     @property
     def embeddings(self):
-        """The fp32 rows (None for a bf16 index built with keep_fp32=False)."""
+        """The fp32 rows (None for a bf16 or fp8 index built with keep_fp32=False)."""
         return self._fp32
 
     def _rows(self):
-        return self._bf16 if self._dtype == 'bf16' else self._fp32
+        return {'bf16': self._bf16, 'fp8': self._fp8}.get(self._dtype, self._fp32)
 
     def set_history(self, user_history):
         """Exclude each user's items (user -> iterable of item ids, as build_user_history makes)
@@ -145,16 +159,16 @@ class ItemIndex:
         U = user_emb.detach().float().contiguous()
         if not fused_supported(self.dim):
             cols, val = self._search_staged(U, k, user_ids, hist)
-        elif oversample > 1 and self._dtype == 'bf16':
+        elif oversample > 1 and self._dtype != 'fp32':
             C = min(256, int(oversample) * k, len(self))
-            cand, cval = ops.fused_topk(U, rows, C, user_ids, hist)
+            cand, cval = ops.fused_topk(U, rows, C, user_ids, hist, item_exp=self.scale_exp)
             exact = ops.rescore_rows(U, self._fp32, cand, cval)
             cols = torch.empty(U.shape[0], k, device=U.device, dtype=torch.int32)
             val = torch.empty(U.shape[0], k, device=U.device, dtype=torch.float32)
             _hip.call('rs_topk_rows', exact.data_ptr(), C, int(U.shape[0]), C, k, cand.data_ptr(), C, 0,
                       cols.data_ptr(), val.data_ptr(), k, ops.stream())
         else:
-            cols, val = ops.fused_topk(U, rows, k, user_ids, hist)
+            cols, val = ops.fused_topk(U, rows, k, user_ids, hist, item_exp=self.scale_exp)
         return self.item_ids[cols.long()], val, cols
 
     def columns_of(self, item_ids):
@@ -192,7 +206,7 @@ class ItemIndex:
         if cols.numel() != U.shape[0]:
             raise ValueError(f'{cols.numel()} target items for {U.shape[0]} users')
         if fused_supported(self.dim):
-            return ops.target_rank(U, rows, cols, user_ids, hist)
+            return ops.target_rank(U, rows, cols, user_ids, hist, item_exp=self.scale_exp)
         return self._rank_staged(U, cols, user_ids, hist)
 
     def _rank_staged(self, U, cols, user_ids, hist, chunk=65536):

@@ -3,10 +3,11 @@
 events: per shape a warm-up of both, then alternating rounds, the median per path and the spread.
 The rank kernel does the top-K kernel's loads and MFMAs and none of its list work, so the
 expectation to check is rank <= top-K per shape. Shapes: B = 4096; N in {3,706, 1,000,000,
-10,000,000}; D in {64, 128}; fp32 and bf16 items; without and with a history of about 100 items
+10,000,000}; D in {64, 128}; fp32, bf16 and e4m3 items (--dtypes); without and with a history of about 100 items
 per user. Each line also says whether rank < K agreed with membership in the top-K list.
 
-    python tools/rank_time.py [--b 4096] [--ns 3706,1000000,10000000] [--ds 64,128] [--k 20] [--out FILE]
+    python tools/rank_time.py [--b 4096] [--ns 3706,1000000,10000000] [--ds 64,128] [--k 20]
+                              [--dtypes fp32,bf16,fp8] [--out FILE]
 """
 import argparse
 import os
@@ -36,6 +37,7 @@ def main():
     ap.add_argument('--ns', default='3706,1000000,10000000')
     ap.add_argument('--ds', default='64,128')
     ap.add_argument('--k', type=int, default=20)
+    ap.add_argument('--dtypes', default='fp32,bf16,fp8')
     ap.add_argument('--history', type=int, default=100)
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--out', default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
@@ -57,12 +59,16 @@ def main():
             tcols = torch.randint(0, N, (B,), device=dev, generator=g).int()
             hist = random_history(B, N, a.history, dev, g)
             uids = torch.arange(B, device=dev)
-            for dtype in ('fp32', 'bf16'):
-                items = I if dtype == 'fp32' else I.bfloat16()
+            for dtype in a.dtypes.split(','):
+                exp = None
+                if dtype == 'fp8':
+                    items, exp = ops.quantize_e4m3(I)
+                else:
+                    items = I if dtype == 'fp32' else I.bfloat16()
                 for with_hist in (False, True):
                     u, h = (uids, hist) if with_hist else (None, None)
-                    paths = {'rank': lambda: ops.target_rank(U, items, tcols, u, h),
-                             'topk': lambda: ops.fused_topk(U, items, K, u, h)}
+                    paths = {'rank': lambda: ops.target_rank(U, items, tcols, u, h, item_exp=exp),
+                             'topk': lambda: ops.fused_topk(U, items, K, u, h, item_exp=exp)}
                     rank = paths['rank']()
                     top = paths['topk']()[0]
                     torch.cuda.synchronize()

@@ -1,6 +1,7 @@
 """Time top-K retrieval three ways on the same seeded inputs, with device events: the staged
 retrieval_topk (fp32 GEMM per 65,536-column chunk -> top-K per chunk -> merge), the fused kernel on
-fp32 items and the fused kernel on bf16 items (ops.fused_topk). Three alternating rounds after a
+fp32 items, on bf16 items and on e4m3 items (ops.fused_topk; the e4m3 rows from
+ops.quantize_e4m3, their scores on the bf16 MFMA). Three alternating rounds after a
 warm-up of every path; per path the three times, their spread, and the share of the binding floor
 (the dot products at the MFMA peak of the item dtype, or the item matrix read once from HBM,
 whichever is larger; the line says which binds). No history.
@@ -17,13 +18,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from recommendsystemproject_amd import _hip, ops  # noqa: E402
 from recommendsystemproject_amd.project.utils.training_utils import retrieval_topk  # noqa: E402
 
-PEAK_TF = {'fp32': 157.3, 'bf16': 2500.0}  # dense MFMA peaks (datasheet), TFLOP/s
+PEAK_TF = {'fp32': 157.3, 'bf16': 2500.0, 'fp8': 2500.0}  # dense MFMA peaks (datasheet), TFLOP/s; e4m3 rows run on the bf16 MFMA
+ITEM_BYTES = {'fp32': 4, 'bf16': 2, 'fp8': 1}
 PEAK_HBM = 8.0e12                            # bytes/s (datasheet)
 
 
 def floor_ms(B, N, D, dtype):
     mfma = 2.0 * B * N * D / (PEAK_TF[dtype] * 1e12) * 1e3
-    mem = N * D * (4 if dtype == 'fp32' else 2) / PEAK_HBM * 1e3
+    mem = N * D * ITEM_BYTES[dtype] / PEAK_HBM * 1e3
     return (mfma, 'MFMA rate') if mfma >= mem else (mem, 'item-matrix bytes')
 
 
@@ -52,16 +54,19 @@ def main():
     g = torch.Generator(device=dev).manual_seed(0)
     I = torch.nn.functional.normalize(torch.randn(a.n, a.d, device=dev, generator=g), dim=1)
     Ib = I.bfloat16()
+    Iq, exp = ops.quantize_e4m3(I)
     lines = [f'top-K retrieval, N = {a.n}, D = {a.d}, K = {a.k}, no history; ms per call (device events), '
              f'{a.rounds} alternating rounds after warm-up']
     for B in [int(x) for x in a.batches.split(',')]:
         U = torch.nn.functional.normalize(torch.randn(B, a.d, device=dev, generator=g), dim=1)
         paths = [('staged fp32', 'fp32', lambda: retrieval_topk(U, I, a.k), 2 if B > 256 else 10),
                  ('fused fp32', 'fp32', lambda: ops.fused_topk(U, I, a.k), 5 if B > 256 else 20),
-                 ('fused bf16', 'bf16', lambda: ops.fused_topk(U, Ib, a.k), 10 if B > 256 else 20)]
+                 ('fused bf16', 'bf16', lambda: ops.fused_topk(U, Ib, a.k), 10 if B > 256 else 20),
+                 ('fused fp8', 'fp8', lambda: ops.fused_topk(U, Iq, a.k, item_exp=exp), 10 if B > 256 else 20)]
         staged = retrieval_topk(U, I, a.k)
         f32 = ops.fused_topk(U, I, a.k)[0]
         ops.fused_topk(U, Ib, a.k)
+        ops.fused_topk(U, Iq, a.k, item_exp=exp)
         torch.cuda.synchronize()
         same = float((staged == f32).all(dim=1).float().mean())
         times = {name: [] for name, _, _, _ in paths}
