@@ -13,13 +13,27 @@ on the device (graph-replay safe) and the backward re-derives the same masks fro
   MLP hidden layer j: 256+j
 With p = 0 (the parity setting) nothing is hashed.
 
+The sequence encoder's forward has several kernels for the same stage; which of them run is decided
+once per forward, before the first launch, by plan_encoder -> EncoderPlan: qkv_bf16 (the packed qkv
+stored as bf16), head ('fused': rs_seq_head_fwd_bf16 for the sequence input and layer 0's qkv, or
+'separate') and per layer a LayerPlan: rows (the pruned last layer) and post, one of POST_ROUTES:
+  'tail_qkv'  rs_layer_tail_fwd_bf16, which also emits the next layer's qkv
+  'tail'      rs_layer_tail_fwd_bf16
+  'ffn'       out-proj + LN1, then rs_ffn_fwd_bf16
+  'separate'  out-proj + LN1, linear1, linear2 + LN2
+seq_input_fwd, layer_fwd and layer_fwd_last follow the plan; each layer keeps a LayerSaved whose
+`post` selects its backward. Only the backward's own fusions (ops.*_bwd_fused_ok), which depend on
+the gradient tensors autograd hands in, are chosen in the backward.
+
 `need` (first argument of every forward) is torch.is_grad_enabled() at the call site: inside
 Function.forward grad mode is always off, so the modules decide whether to keep activations.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
+from typing import NamedTuple, Tuple
 
 import torch
 from torch.autograd.function import once_differentiable
@@ -294,13 +308,14 @@ def seq_feature_segments(proc, seqd, B, L):
     return segs, tables, col, keep
 
 
-def seq_input_fwd(proc, seqd, B, L, p, key, err, need=True, attn=None):
-    """gather -> Linear(sum dims -> d) -> Dropout -> + pos_emb -> F.dropout (T5). Returns
-    (x [B*L, d], the backward's saved state, qkv0). attn: the first encoder layer's attention
-    module; where the fused sequence head takes the call (ops.seq_head_ok) one kernel does all of
-    it from the ids and also emits that layer's packed in-projection qkv0 (bf16): cat is written
-    for the backward but not read back, x0 is not read back either. Otherwise qkv0 is None."""
-    segs, tables, dcat, keep = seq_feature_segments(proc, seqd, B, L)
+def seq_input_fwd(proc, feats, B, L, p, key, err, need=True, attn=None):
+    """gather -> Linear(sum dims -> d) -> Dropout -> + pos_emb -> F.dropout (T5) on feats, the
+    result of seq_feature_segments. Returns (x [B*L, d], the backward's saved state, qkv0). attn:
+    the first encoder layer's attention module where the plan's head is 'fused' (plan_encoder):
+    one kernel does all of it from the ids and also emits that layer's packed in-projection qkv0
+    (bf16): cat is written for the backward but not read back, x0 is not read back either. None:
+    the separate kernels, qkv0 is None."""
+    segs, tables, dcat, keep = feats
     if dcat != proc.feature_projection[0].in_features:
         raise RuntimeError(f'mat1 and mat2 shapes cannot be multiplied ({B * L}x{dcat} and '
                            f'{proc.feature_projection[0].in_features}x{proc.target_dim})')
@@ -309,9 +324,7 @@ def seq_input_fwd(proc, seqd, B, L, p, key, err, need=True, attn=None):
     calls, lazy = _lookup_lazy(segs, tables, M, keep, record=need, err=err)
     lin = proc.feature_projection[0]
     pos = proc.pos_emb.weight
-    # ordinary tables only: no lazy-Adam call (catch-up, sharded rows, data-parallel exchange)
-    plain = not calls and lazy is None and not any(hasattr(t, '_rs_lazy') for t in tables)
-    if attn is not None and plain and ops.seq_head_ok(segs, M, L, dcat, lin, pos, attn):
+    if attn is not None:  # ordinary tables only (the plan): no lazy-Adam call came out of the lookup
         x, cat, qkv = ops.seq_head_fwd(segs, M, L, dcat, lin.weight, lin.bias, pos, attn.in_proj_weight,
                                        attn.in_proj_bias, err, p, key, 0, 1)
         return x, (segs, tables, cat, keep, calls), qkv
@@ -375,7 +388,7 @@ class SeqFeaturesFn(torch.autograd.Function):
             raise IndexError('index out of range in self')
         p = proc.dropout if proc.training else 0.0
         key = ops.rng_next(proc.rng_state) if p > 0 else None
-        x, saved, _ = seq_input_fwd(proc, seqd, B, L, p, key, proc.err_flag, need)
+        x, saved, _ = seq_input_fwd(proc, seq_feature_segments(proc, seqd, B, L), B, L, p, key, proc.err_flag, need)
         if need:
             ctx.proc, ctx.saved, ctx.B, ctx.L, ctx.p, ctx.key = proc, saved, B, L, p, key
             ctx.params = params
@@ -393,75 +406,33 @@ class SeqFeaturesFn(torch.autograd.Function):
 
 
 # ================================================================================ encoder layer
-def _is_fake(t):
-    from torch._subclasses.fake_tensor import FakeTensor
-    return isinstance(t, FakeTensor)
+POST_ROUTES = ('tail_qkv', 'tail', 'ffn', 'separate')
 
 
-def _ffn_fwd(lyr, x1, p, key, site):
-    """x2 = norm2(x1 + dropout2(linear2(dropout(relu(linear1(x1)))))) on any row count."""
-    if ops.ffn_supported(x1, lyr.linear1.weight):
-        # bf16 mode: the whole feed-forward block in one kernel; f1 stays on chip (csrc/ffn.hip)
-        h2, x2, m2, r2, fmask = ops.ffn_fwd_bf16(x1, lyr.linear1.weight, lyr.linear1.bias,
-                                                 lyr.linear2.weight, lyr.linear2.bias, lyr.norm2.weight,
-                                                 lyr.norm2.bias, lyr.norm2.eps, p, key, site + 2, site + 3)
-        return x2, (('ffn', fmask), h2, m2, r2)
-    f1 = ops.linear_fwd(x1, lyr.linear1.weight, lyr.linear1.bias, relu=True, drop_p=p, drop_key=key,
-                        site_a=site + 2)  # dropout(relu(.)) fused
-    h2, x2, m2, r2 = ops.linear_add_layernorm(f1, lyr.linear2.weight, lyr.linear2.bias, x1,
-                                              lyr.norm2.weight, lyr.norm2.bias, lyr.norm2.eps, p, key,
-                                              site + 3)  # h2 = x1 + dropout2(ff), x2 = norm2(h2)
-    return x2, (f1, h2, m2, r2)
+class LayerPlan(NamedTuple):
+    """One encoder layer's kernels. rows: the pruned last layer (its post-attention half on the B
+    selected rows). post, what follows the attention: 'tail_qkv' / 'tail', rs_layer_tail_fwd_bf16
+    with / without the next layer's qkv; 'ffn', out-proj + LN1, then rs_ffn_fwd_bf16; 'separate',
+    out-proj + LN1, linear1, linear2 + LN2. resid_in_place (a rows layer): out-proj + LN1 reads its
+    residual rows in place (rs_gemm_add_layernorm_rows) instead of gathering them first."""
+    rows: bool
+    post: str
+    resid_in_place: bool
 
 
-def _in_proj_fwd(sa_mod, x, B, L, d, H):
-    # bf16 mode: qkv stored as bf16 (only ever an MFMA operand: same products, half the bytes)
-    return ops.linear_fwd(x, sa_mod.in_proj_weight, sa_mod.in_proj_bias,
-                          out_dtype=torch.bfloat16 if ops.qkv_bf16_ok(L, d, H, B * L) else torch.float32)
+class EncoderPlan(NamedTuple):
+    """plan_encoder's answer. qkv_bf16: every layer's packed qkv is stored as bf16
+    (ops.qkv_bf16_ok). head: 'fused', rs_seq_head_fwd_bf16 computes the sequence input and layer
+    0's qkv; 'separate', gather + projection, and layer 0 runs its own in-projection."""
+    qkv_bf16: bool
+    head: str
+    layers: Tuple[LayerPlan, ...]
 
 
-def _tail_ok(lyr, att, x, nxt=None):
-    """The layer's forward tail as one kernel (ops.layer_tail_fwd): every bias of the layer present;
-    nxt: the next layer's attention module when the kernel is also to emit that layer's qkv."""
-    sa_mod = lyr.self_attn
-    return (sa_mod.out_proj.bias is not None and lyr.linear1.bias is not None and lyr.linear2.bias is not None and
-            ops.layer_tail_ok(att, x, lyr.linear1.weight, sa_mod.out_proj.weight,
-                              None if nxt is None else nxt.in_proj_weight))
-
-
-def layer_fwd(lyr, x, key_pad, B, L, d, H, p, key, site, qkv=None, next_attn=None):
-    """nn.TransformerEncoderLayer (norm_first=False, relu) forward on x [B*L, d]. qkv: this layer's
-    packed in-projection when the previous stage already computed it. next_attn: the next layer's
-    attention module; a third value is then returned, that layer's qkv (bf16) from the fused tail
-    kernel, or None where it does not run."""
-    sa_mod = lyr.self_attn
-    if qkv is None:
-        qkv = _in_proj_fwd(sa_mod, x, B, L, d, H)
-    att, lse = ops.attn_fwd(qkv, key_pad, B, L, d, H, p, key, site)
-    # the fused tail where the token count is the bf16 streaming kernels' (ops.qkv_bf16_ok); it emits
-    # the next layer's qkv too when that layer has an in-projection bias (else that layer computes it)
-    chain = ops.qkv_bf16_ok(L, d, H, B * L)
-    nxt = next_attn if next_attn is not None and next_attn.in_proj_bias is not None else None
-    if chain and nxt is not None and not _tail_ok(lyr, att, x, nxt):
-        nxt = None  # an in-projection the kernel does not take: the tail without qkv
-    if chain and _tail_ok(lyr, att, x, nxt):
-        # bf16 mode: out-proj + LN1 + FFN + LN2 (+ the next layer's qkv) in one pass; x1 and x2 go
-        # from stage to stage on chip (csrc/ffn.hip rs_layer_tail_fwd_bf16)
-        h1, x1, m1, r1, h2, x2, m2, r2, fmask, qn = ops.layer_tail_fwd(
-            att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, x, lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps,
-            lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, lyr.linear2.bias, lyr.norm2.weight,
-            lyr.norm2.bias, lyr.norm2.eps, p, key, site,
-            Win=None if nxt is None else nxt.in_proj_weight, bin_=None if nxt is None else nxt.in_proj_bias,
-            store_x1=False)  # x1 is None: the weight gradients rebuild it from h1 (ops.ffn_wgrad_ln_bf16)
-        s = (x, qkv, att, lse, h1, x1, m1, r1, ('ffn', fmask), h2, m2, r2)
-        return (x2, s) if next_attn is None else (x2, s, qn)
-    # h1 = x + dropout1(out_proj(att)), x1 = norm1(h1): GEMM + residual + LayerNorm in one kernel
-    h1, x1, m1, r1 = ops.linear_add_layernorm(att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, x,
-                                              lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps, p, key,
-                                              site + 1)
-    x2, ff = _ffn_fwd(lyr, x1, p, key, site)
-    s = (x, qkv, att, lse, h1, x1, m1, r1) + ff
-    return (x2, s) if next_attn is None else (x2, s, None)
+# What a layer's forward keeps for its backward. Exactly one of f1 (linear1's output, the 'separate'
+# route) and fmask (the fused FFN's keep / sign mask) is set; x1 is None on the tail routes only (the
+# weight gradients rebuild it from h1, m1, r1); post: the LayerPlan's
+LayerSaved = collections.namedtuple('LayerSaved', 'x qkv att lse h1 x1 m1 r1 f1 fmask h2 m2 r2 post')
 
 
 def prune_last_layer() -> bool:
@@ -471,81 +442,177 @@ def prune_last_layer() -> bool:
     return not os.environ.get('RSYS_FULL_LAST_LAYER')
 
 
-def layer_fwd_last(lyr, x, key_pad, last, B, L, d, H, p, key, site, qkv=None):
-    """The final encoder layer for the selected rows last[b] only -> x2 [B, d] (= the encoder
-    output): qkv for all rows (every key / value is live; given, or computed here), attention of
-    the B selected queries, then out-proj + LN1 + FFN + LN2 on B rows."""
+def _post_route(lyr, nxt, rows, pruned, qkv_bf16):
+    """A layer's LayerPlan.post on `rows` rows; nxt: the next layer's attention module or None."""
     sa_mod = lyr.self_attn
-    if qkv is None:
-        qkv = _in_proj_fwd(sa_mod, x, B, L, d, H)
+    W1 = lyr.linear1.weight
+    # the fused tail: the full layers, where the token count is the bf16 streaming kernels'
+    # (qkv_bf16) and every bias of the layer is present; it emits the next layer's qkv too when that
+    # layer has an in-projection bias and a Win the kernel takes (else that layer computes it)
+    if (not pruned and qkv_bf16 and sa_mod.out_proj.bias is not None and lyr.linear1.bias is not None and
+            lyr.linear2.bias is not None and ops.layer_tail_ok(rows, W1, sa_mod.out_proj.weight)):
+        emit = nxt is not None and nxt.in_proj_bias is not None and ops.layer_tail_qkv_ok(nxt.in_proj_weight)
+        return 'tail_qkv' if emit else 'tail'
+    return 'ffn' if ops.ffn_supported(rows, W1) else 'separate'
+
+
+def plan_encoder(enc, segs, tables, B, L) -> EncoderPlan:
+    """Which kernels one SequenceEncoder forward on [B, L] runs, decided once from the shapes, the
+    compute mode, the RSYS_* switches, the layers' weights and whether a sequence table is lazy
+    (segs, tables: seq_feature_segments'). Launches nothing and follows no pointer. The tensors the
+    encoder allocates itself (each layer's input and attention output: fresh, contiguous, fp32) are
+    not tested here; the ops and entry points guard them. The backward's own choices
+    (ops.*_bwd_fused_ok) depend on the gradient tensors autograd hands in and stay there."""
+    proc = enc.feature_embedder
+    layers = list(enc.transformer_backbone.layers)
+    n, M, d = len(layers), B * L, proc.target_dim
+    qkv_bf16 = ops.qkv_bf16_ok(L, d, enc.n_head, M)
+    lin = proc.feature_projection[0]
+    fused = (n > 0 and not any(hasattr(t, '_rs_lazy') for t in tables) and
+             ops.seq_head_ok(segs, M, L, sum(s.dim for s in segs), lin, proc.pos_emb.weight, layers[0].self_attn,
+                             qkv_bf16=qkv_bf16))
+    prune = prune_last_layer() and L <= 256
+    plans = []
+    for i, lyr in enumerate(layers):
+        rows = prune and i == n - 1
+        nxt = layers[i + 1].self_attn if i + 1 < n else None
+        plans.append(LayerPlan(rows, _post_route(lyr, nxt, B if rows else M, rows, qkv_bf16),
+                               rows and ops.linear_add_layernorm_rows_ok(B, lyr.self_attn.out_proj.weight)))
+    return EncoderPlan(qkv_bf16, 'fused' if fused else 'separate', tuple(plans))
+
+
+def _in_proj_fwd(sa_mod, x, qkv_bf16):
+    # bf16 mode: qkv stored as bf16 (only ever an MFMA operand: same products, half the bytes)
+    return ops.linear_fwd(x, sa_mod.in_proj_weight, sa_mod.in_proj_bias,
+                          out_dtype=torch.bfloat16 if qkv_bf16 else torch.float32)
+
+
+def _ffn_fwd(lyr, x1, p, key, site, post):
+    """x2 = norm2(x1 + dropout2(linear2(dropout(relu(linear1(x1)))))) on any row count, by route
+    'ffn' or 'separate' -> (x2, f1, fmask, h2, m2, r2)."""
+    if post == 'ffn':
+        # bf16 mode: the whole feed-forward block in one kernel; f1 stays on chip (csrc/ffn.hip)
+        h2, x2, m2, r2, fmask = ops.ffn_fwd_bf16(x1, lyr.linear1.weight, lyr.linear1.bias,
+                                                 lyr.linear2.weight, lyr.linear2.bias, lyr.norm2.weight,
+                                                 lyr.norm2.bias, lyr.norm2.eps, p, key, site + 2, site + 3)
+        return x2, None, fmask, h2, m2, r2
+    f1 = ops.linear_fwd(x1, lyr.linear1.weight, lyr.linear1.bias, relu=True, drop_p=p, drop_key=key,
+                        site_a=site + 2)  # dropout(relu(.)) fused
+    h2, x2, m2, r2 = ops.linear_add_layernorm(f1, lyr.linear2.weight, lyr.linear2.bias, x1,
+                                              lyr.norm2.weight, lyr.norm2.bias, lyr.norm2.eps, p, key,
+                                              site + 3)  # h2 = x1 + dropout2(ff), x2 = norm2(h2)
+    return x2, f1, None, h2, m2, r2
+
+
+def layer_fwd(lyr, x, qkv, key_pad, B, L, d, H, p, key, site, post, next_attn=None):
+    """nn.TransformerEncoderLayer (norm_first=False, relu) forward on x [B*L, d] by route `post`
+    (LayerPlan). qkv: this layer's packed in-projection. next_attn: the next layer's attention
+    module. Returns (x2, LayerSaved, qkv_next): qkv_next is the next layer's qkv (bf16) on route
+    'tail_qkv', else None."""
+    sa_mod = lyr.self_attn
+    att, lse = ops.attn_fwd(qkv, key_pad, B, L, d, H, p, key, site)
+    if post in ('tail_qkv', 'tail'):
+        # bf16 mode: out-proj + LN1 + FFN + LN2 (+ the next layer's qkv) in one pass; x1 and x2 go
+        # from stage to stage on chip (csrc/ffn.hip rs_layer_tail_fwd_bf16)
+        emit = post == 'tail_qkv'
+        h1, x1, m1, r1, h2, x2, m2, r2, fmask, qkv_next = ops.layer_tail_fwd(
+            att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, x, lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps,
+            lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, lyr.linear2.bias, lyr.norm2.weight,
+            lyr.norm2.bias, lyr.norm2.eps, p, key, site,
+            Win=next_attn.in_proj_weight if emit else None, bin_=next_attn.in_proj_bias if emit else None,
+            store_x1=False)  # x1 is None: the weight gradients rebuild it from h1 (ops.ffn_wgrad_ln_bf16)
+        return x2, LayerSaved(x, qkv, att, lse, h1, x1, m1, r1, None, fmask, h2, m2, r2, post), qkv_next
+    # h1 = x + dropout1(out_proj(att)), x1 = norm1(h1): GEMM + residual + LayerNorm in one kernel
+    h1, x1, m1, r1 = ops.linear_add_layernorm(att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, x,
+                                              lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps, p, key,
+                                              site + 1)
+    x2, *ff = _ffn_fwd(lyr, x1, p, key, site, post)
+    return x2, LayerSaved(x, qkv, att, lse, h1, x1, m1, r1, *ff, post), None
+
+
+def layer_fwd_last(lyr, x, qkv, key_pad, last, B, L, d, H, p, key, site, plan):
+    """The final encoder layer for the selected rows last[b] only -> (x2 [B, d] (= the encoder
+    output), LayerSaved): qkv for all rows (every key / value is live), attention of the B selected
+    queries, then out-proj + LN1 + FFN + LN2 on B rows by `plan` (its LayerPlan)."""
+    sa_mod = lyr.self_attn
     att, lse = ops.attn_rows_fwd(qkv, key_pad, last, B, L, d, H, p, key, site)
-    # the residual rows x[b, last[b]] read in place by the fused kernel (bf16 mode), else gathered
-    post = ops.linear_add_layernorm_rows(att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, x, last, L,
-                                         lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps, p, key, site + 1)
-    if post is None:
+    if plan.resid_in_place:  # bf16 mode: the fused kernel reads the residual rows x[b, last[b]] in place
+        h1, x1, m1, r1 = ops.linear_add_layernorm_rows(att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, x, last,
+                                                       L, lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps, p, key,
+                                                       site + 1)
+    else:
         xs = torch.empty(B, d, device=x.device, dtype=torch.float32)
         ops.gather_fwd([_seg(kind=_hip.RS_SEG_LASTVALID, dim=d, out_col=0, bag=L, idx=last.data_ptr(),
                              table=x.data_ptr())], B, xs)
-        post = ops.linear_add_layernorm(att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, xs,
-                                        lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps, p, key, site + 1)
-    h1, x1, m1, r1 = post
-    x2, ff = _ffn_fwd(lyr, x1, p, key, site)
-    return x2, (x, qkv, att, lse, h1, x1, m1, r1) + ff
+        h1, x1, m1, r1 = ops.linear_add_layernorm(att, sa_mod.out_proj.weight, sa_mod.out_proj.bias, xs,
+                                                  lyr.norm1.weight, lyr.norm1.bias, lyr.norm1.eps, p, key, site + 1)
+    x2, *ff = _ffn_fwd(lyr, x1, p, key, site, plan.post)
+    return x2, LayerSaved(x, qkv, att, lse, h1, x1, m1, r1, *ff, plan.post)
 
 
-def _post_attn_bwd(lyr, saved, dx2, p, key, site):
-    """Backward of out-proj + LN1 + FFN + LN2 (any row count). Returns (dh1, datt): dh1 the
-    gradient of the layer input through the residual, datt the gradient of the attention output."""
-    x, qkv, att, lse, h1, x1, m1, r1, f1, h2, m2, r2 = saved
+def _post_attn_bwd_ffn(lyr, s, dx2, p, key, site):
+    """Backward of out-proj + LN1 + FFN + LN2 (any row count) on the routes whose forward ran the
+    fused FFN ('tail_qkv', 'tail', 'ffn'); dx2 is only read. Returns (dh1, datt): dh1 the gradient
+    of the layer input through the residual, datt the gradient of the attention output."""
     g = grad_of
     sa_mod = lyr.self_attn
     Wo, gWo = sa_mod.out_proj.weight, g(sa_mod.out_proj.weight)
-    # bf16 mode, token-sized layer: dsa = drop1(dh1) is never stored; the out-projection's weight,
-    # bias and input gradients come from one read of dh1 (csrc/linear_bwd.hip). dh1 is a fresh
-    # allocation of dx2's shape and layout, so the check runs on dx2
-    fuse = isinstance(f1, tuple) and ops.outproj_bwd_fused_ok(dx2, att, Wo, gWo)
-    # x2 = LN2(x1 + drop2(ff))
-    ln1_done = False
-    if isinstance(f1, tuple):
-        # bf16 mode, fused feed-forward block: norm2 backward + FFN backward + norm1 backward in one
-        # pass (csrc/ffn.hip): dh2 and dx1 stay on chip; dff = drop2(dh2) is written for the fused
-        # weight gradients, which recompute f1 / dPre1 on chip
-        dh1, dsa, dff = ops.ffn_bwd_ln2_bf16(
-            x1, lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, f1[1], dx2, h2, lyr.norm2.weight,
-            m2, r2, g(lyr.norm2.weight), g(lyr.norm2.bias), h1, lyr.norm1.weight, m1, r1,
-            g(lyr.norm1.weight), g(lyr.norm1.bias), p, key, site + 1, site + 3, dsa=not fuse)
-        ln1_done = True
-        if x1 is None:  # the fused forward tail did not store x1 = LN1(h1): rebuilt while staging
-            ops.ffn_wgrad_ln_bf16(h1, m1, r1, lyr.norm1.weight, lyr.norm1.bias, lyr.linear1.weight,
-                                  lyr.linear1.bias, lyr.linear2.weight, f1[1], dff, p, g(lyr.linear1.weight),
-                                  g(lyr.linear1.bias), g(lyr.linear2.weight), g(lyr.linear2.bias))
-        else:
-            ops.ffn_wgrad_bf16(x1, lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, f1[1], dff, p,
-                               g(lyr.linear1.weight), g(lyr.linear1.bias), g(lyr.linear2.weight),
-                               g(lyr.linear2.bias))
-    else:
-        dff = torch.empty_like(dx2) if p > 0 else None
-        dh2 = ops.layernorm_bwd(h2, dx2, lyr.norm2.weight, m2, r2, g(lyr.norm2.weight), g(lyr.norm2.bias),
-                                da=dff, p=p, key=key, site=site + 3)
-        dff = dh2 if dff is None else dff
-        ops.linear_bwd_weight(dff, f1, g(lyr.linear2.weight), db=g(lyr.linear2.bias))
-        # f1 holds relu(.) after dropout: (f1 > 0) == kept & positive, kept scale 1/(1-p)
-        df1 = ops.linear_bwd_input(dff, lyr.linear2.weight, relu_mask_of=f1,
-                                   alpha=(1.0 / (1.0 - p)) if p > 0 else 1.0)
-        ops.linear_bwd_weight(df1, x1, g(lyr.linear1.weight), db=g(lyr.linear1.bias))
-        ops.linear_bwd_input(df1, lyr.linear1.weight, out=dh2, beta=1.0)  # dx1 = dh2 + df1 W1
-    # x1 = LN1(x + drop1(sa))
-    if not ln1_done:
-        dsa = torch.empty_like(dh2) if p > 0 else None
-        dh1 = ops.layernorm_bwd(h1, dh2, lyr.norm1.weight, m1, r1, g(lyr.norm1.weight), g(lyr.norm1.bias),
-                                da=dsa, p=p, key=key, site=site + 1)
+    # token-sized layer: dsa = drop1(dh1) is never stored; the out-projection's weight, bias and
+    # input gradients come from one read of dh1 (csrc/linear_bwd.hip). dh1 is a fresh allocation of
+    # dx2's shape and layout, so the check runs on dx2
+    fuse = ops.outproj_bwd_fused_ok(dx2, s.att, Wo, gWo)
+    # norm2 backward + FFN backward + norm1 backward in one pass (csrc/ffn.hip): dh2 and dx1 stay on
+    # chip; dff = drop2(dh2) is written for the fused weight gradients, which recompute f1 / dPre1
+    # on chip
+    dh1, dsa, dff = ops.ffn_bwd_ln2_bf16(
+        s.x1, lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, s.fmask, dx2, s.h2, lyr.norm2.weight,
+        s.m2, s.r2, g(lyr.norm2.weight), g(lyr.norm2.bias), s.h1, lyr.norm1.weight, s.m1, s.r1,
+        g(lyr.norm1.weight), g(lyr.norm1.bias), p, key, site + 1, site + 3, dsa=not fuse)
+    if s.post == 'ffn':
+        ops.ffn_wgrad_bf16(s.x1, lyr.linear1.weight, lyr.linear1.bias, lyr.linear2.weight, s.fmask, dff, p,
+                           g(lyr.linear1.weight), g(lyr.linear1.bias), g(lyr.linear2.weight),
+                           g(lyr.linear2.bias))
+    else:  # the fused forward tail did not store x1 = LN1(h1): rebuilt while staging
+        ops.ffn_wgrad_ln_bf16(s.h1, s.m1, s.r1, lyr.norm1.weight, lyr.norm1.bias, lyr.linear1.weight,
+                              lyr.linear1.bias, lyr.linear2.weight, s.fmask, dff, p, g(lyr.linear1.weight),
+                              g(lyr.linear1.bias), g(lyr.linear2.weight), g(lyr.linear2.bias))
     if fuse:
-        return dh1, ops.outproj_bwd_fused(dh1, att, Wo, p, key, site + 1, gWo, g(sa_mod.out_proj.bias))
+        return dh1, ops.outproj_bwd_fused(dh1, s.att, Wo, p, key, site + 1, gWo, g(sa_mod.out_proj.bias))
     if dsa is None:  # p == 0: dsa IS dh1 (read here before the in-proj backward accumulates into it)
         dsa = dh1
-    ops.linear_bwd_weight(dsa, att, gWo, db=g(sa_mod.out_proj.bias))
-    datt = ops.linear_bwd_input(dsa, Wo)
-    return dh1, datt
+    ops.linear_bwd_weight(dsa, s.att, gWo, db=g(sa_mod.out_proj.bias))
+    return dh1, ops.linear_bwd_input(dsa, Wo)
+
+
+def _post_attn_bwd_separate(lyr, s, dx2, p, key, site):
+    """_post_attn_bwd_ffn's counterpart for route 'separate': one kernel per stage; norm2's backward
+    runs in place over dx2, which is consumed."""
+    g = grad_of
+    sa_mod = lyr.self_attn
+    # x2 = LN2(x1 + drop2(ff)); p == 0: dff IS dh2
+    dff = torch.empty_like(dx2) if p > 0 else None
+    dh2 = ops.layernorm_bwd(s.h2, dx2, lyr.norm2.weight, s.m2, s.r2, g(lyr.norm2.weight), g(lyr.norm2.bias),
+                            da=dff, p=p, key=key, site=site + 3)
+    dff = dh2 if dff is None else dff
+    ops.linear_bwd_weight(dff, s.f1, g(lyr.linear2.weight), db=g(lyr.linear2.bias))
+    # f1 holds relu(.) after dropout: (f1 > 0) == kept & positive, kept scale 1/(1-p)
+    df1 = ops.linear_bwd_input(dff, lyr.linear2.weight, relu_mask_of=s.f1,
+                               alpha=(1.0 / (1.0 - p)) if p > 0 else 1.0)
+    ops.linear_bwd_weight(df1, s.x1, g(lyr.linear1.weight), db=g(lyr.linear1.bias))
+    ops.linear_bwd_input(df1, lyr.linear1.weight, out=dh2, beta=1.0)  # dx1 = dh2 + df1 W1
+    # x1 = LN1(x + drop1(sa)); p == 0: dsa IS dh1 (read here before the in-proj backward accumulates
+    # into it)
+    dsa = torch.empty_like(dh2) if p > 0 else None
+    dh1 = ops.layernorm_bwd(s.h1, dh2, lyr.norm1.weight, s.m1, s.r1, g(lyr.norm1.weight), g(lyr.norm1.bias),
+                            da=dsa, p=p, key=key, site=site + 1)
+    dsa = dh1 if dsa is None else dsa
+    ops.linear_bwd_weight(dsa, s.att, g(sa_mod.out_proj.weight), db=g(sa_mod.out_proj.bias))
+    return dh1, ops.linear_bwd_input(dsa, sa_mod.out_proj.weight)
+
+
+def _post_attn_bwd(lyr, s, dx2, p, key, site):
+    bwd = _post_attn_bwd_separate if s.post == 'separate' else _post_attn_bwd_ffn
+    return bwd(lyr, s, dx2, p, key, site)
 
 
 def _in_proj_bwd(lyr, x, dqkv, dx=None):
@@ -567,18 +634,16 @@ def _in_proj_bwd(lyr, x, dqkv, dx=None):
 
 def layer_bwd(lyr, saved, dx2, key_pad, B, L, d, H, p, key, site):
     """Backward of layer_fwd. dx2 is consumed; returns dx [B*L, d]."""
-    x, qkv, lse = saved[0], saved[1], saved[3]
     dh1, datt = _post_attn_bwd(lyr, saved, dx2, p, key, site)
-    dqkv = ops.attn_bwd(qkv, key_pad, saved[2], datt, lse, B, L, d, H, p, key, site)
-    return _in_proj_bwd(lyr, x, dqkv, dx=dh1)
+    dqkv = ops.attn_bwd(saved.qkv, key_pad, saved.att, datt, saved.lse, B, L, d, H, p, key, site)
+    return _in_proj_bwd(lyr, saved.x, dqkv, dx=dh1)
 
 
 def layer_bwd_last(lyr, saved, dx2, key_pad, last, B, L, d, H, p, key, site):
     """Backward of layer_fwd_last: dx2 [B, d] (the encoder output's gradient) -> dx [B*L, d]."""
-    x, qkv, lse = saved[0], saved[1], saved[3]
     dh1, datt = _post_attn_bwd(lyr, saved, dx2, p, key, site)
-    dqkv = ops.attn_rows_bwd(qkv, key_pad, last, datt, lse, B, L, d, H, p, key, site)
-    dx = _in_proj_bwd(lyr, x, dqkv)
+    dqkv = ops.attn_rows_bwd(saved.qkv, key_pad, last, datt, saved.lse, B, L, d, H, p, key, site)
+    dx = _in_proj_bwd(lyr, saved.x, dqkv)
     # the residual rows x[b, last[b]] got dh1: add it back at those rows
     ops.gather_bwd([_seg(kind=_hip.RS_SEG_LASTVALID, dim=d, out_col=0, bag=L, idx=last.data_ptr(),
                          grad=dx.data_ptr())], B, dh1)
@@ -614,21 +679,23 @@ class SeqEncoderFn(torch.autograd.Function):
         layers = list(enc.transformer_backbone.layers)
         if enc.transformer_backbone.norm is not None:
             raise NotImplementedError('TransformerEncoder(norm=...) is not used by the reference')
+        feats = seq_feature_segments(proc, seqd, B, L)
+        plan = plan_encoder(enc, feats[0], feats[1], B, L)
         # qkv: a layer's in-projection where the stage before it computed it (the fused sequence
-        # head for layer 0, the previous layer's fused tail after that)
-        x, in_saved, qkv = seq_input_fwd(proc, seqd, B, L, p, key, err, need,
-                                         attn=layers[0].self_attn if layers else None)
-        prune = prune_last_layer() and len(layers) > 0 and L <= 256
+        # head for layer 0, the previous layer's fused tail after that), else None
+        x, in_saved, qkv = seq_input_fwd(proc, feats, B, L, p, key, err, need,
+                                         attn=layers[0].self_attn if plan.head == 'fused' else None)
         saved = []
-        for i, lyr in enumerate(layers):
-            if prune and i == len(layers) - 1:
-                x, s = layer_fwd_last(lyr, x, key_pad, last, B, L, d, H, p, key, _layer_site(i), qkv=qkv)
-            elif i + 1 < len(layers):
-                x, s, qkv = layer_fwd(lyr, x, key_pad, B, L, d, H, p, key, _layer_site(i), qkv=qkv,
-                                      next_attn=layers[i + 1].self_attn)
+        for i, (lyr, lp) in enumerate(zip(layers, plan.layers)):
+            if qkv is None:
+                qkv = _in_proj_fwd(lyr.self_attn, x, plan.qkv_bf16)
+            if lp.rows:
+                x, s = layer_fwd_last(lyr, x, qkv, key_pad, last, B, L, d, H, p, key, _layer_site(i), lp)
             else:
-                x, s = layer_fwd(lyr, x, key_pad, B, L, d, H, p, key, _layer_site(i), qkv=qkv)
+                x, s, qkv = layer_fwd(lyr, x, qkv, key_pad, B, L, d, H, p, key, _layer_site(i), lp.post,
+                                      next_attn=layers[i + 1].self_attn if i + 1 < len(layers) else None)
             saved.append(s)
+        prune = bool(layers) and plan.layers[-1].rows
         if prune:
             out = x  # [B, d]: the final layer produced the selected rows only
         else:
@@ -659,10 +726,10 @@ class SeqEncoderFn(torch.autograd.Function):
         from .flat import _dp_active
         with ops.deferred_reduce(not _dp_active()):
             if ctx.prune:
-                # the fused bf16 FFN backward only reads the output gradient; the fp32 path's
+                # the fused FFN backward only reads the output gradient; the 'separate' route's
                 # norm2 backward runs in place over it (autograd's buffer: give it a copy)
                 ls = ctx.layer_saved[n - 1]
-                d_last = dout if isinstance(ls[8], tuple) else dout.clone()
+                d_last = dout.clone() if ls.post == 'separate' else dout
                 dx = layer_bwd_last(ctx.layers[n - 1], ls, d_last, ctx.key_pad,
                                     ctx.last, B, L, d, H, p, key, _layer_site(n - 1))
                 n -= 1

@@ -98,7 +98,8 @@ def _alias_outputs(v, ids):
     if isinstance(v, list):
         return [_alias_outputs(x, ids) for x in v]
     if isinstance(v, tuple):
-        return tuple(_alias_outputs(x, ids) for x in v)
+        out = tuple(_alias_outputs(x, ids) for x in v)
+        return type(v)(*out) if hasattr(v, '_fields') else out  # a named tuple stays one
     return v
 
 

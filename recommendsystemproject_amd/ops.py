@@ -129,11 +129,11 @@ def linear_bwd_weight(dy, x, dW, *, beta=1.0, db=None):
                 ldc=dW.stride(0), beta=beta, rowsum=db)
 
 
-def ffn_supported(x, W1):
-    """The fused feed-forward block: bf16 compute mode, d_model 64, dim_feedforward 256."""
+def ffn_supported(rows, W1):
+    """The fused feed-forward block on `rows` rows: bf16 compute mode, d_model 64, dim_feedforward
+    256 (W1 [256, 64]), rows a multiple of 16."""
     return (precision.compute_dtype() == 'bf16' and not os.environ.get('RSYS_UNFUSED_FFN') and
-            x.dim() == 2 and x.shape[1] == 64 and
-            tuple(W1.shape) == (256, 64) and x.shape[0] % 16 == 0 and x.is_contiguous())
+            tuple(W1.shape) == (256, 64) and rows % 16 == 0)
 
 
 def ffn_fwd_bf16(x, W1, b1, W2, b2, gamma, beta, eps, p, key, site1, site2):
@@ -453,15 +453,22 @@ def linear_add_layernorm(x, W, bias, resid, gamma, beta, eps=1e-5, p=0.0, key=No
     return h, y, mean, rstd
 
 
+def linear_add_layernorm_rows_ok(M, W):
+    """rs_gemm_add_layernorm_rows takes M rows through W [64, K]: bf16 MFMA mode, M a multiple of
+    16, K 64 or 256."""
+    return bool(precision.gemm_flags() & _hip.RS_GEMM_BF16) and M % 16 == 0 and W.dim() == 2 and \
+        W.shape[0] == 64 and W.shape[1] in (64, 256) and W.stride(0) % 4 == 0
+
+
 def linear_add_layernorm_rows(x, W, bias, table, rows, bag, gamma, beta, eps=1e-5, p=0.0, key=None, site=0):
     """linear_add_layernorm with the residual rows read in place: row m's residual is
-    table[m * bag + rows[m]] (rs_gemm_add_layernorm_rows). None when the fused bf16 kernel does not
-    take the shape (the caller gathers the rows instead)."""
+    table[m * bag + rows[m]] (rs_gemm_add_layernorm_rows). Only where linear_add_layernorm_rows_ok
+    holds (elsewhere the caller gathers the rows and runs linear_add_layernorm)."""
     M, K = x.shape
     N = W.shape[0]
-    if not (precision.gemm_flags() & _hip.RS_GEMM_BF16) or M % 16 or N != 64 or K not in (64, 256) or \
-            x.stride(0) % 4 or W.stride(0) % 4 or rows.dtype != torch.int64 or not table.is_contiguous():
-        return None
+    if not linear_add_layernorm_rows_ok(M, W) or K != W.shape[1] or x.stride(0) % 4 or \
+            rows.dtype != torch.int64 or not table.is_contiguous():
+        raise RuntimeError('linear_add_layernorm_rows: a shape or layout the fused bf16 kernel does not take')
     dev = x.device
     h = torch.empty(M, N, device=dev, dtype=torch.float32)
     y = torch.empty(M, N, device=dev, dtype=torch.float32)
@@ -483,16 +490,20 @@ def _rowmajor(W, cols):
     return W.dim() == 2 and W.shape[1] == cols and W.stride(1) == 1 and W.stride(0) % 4 == 0
 
 
-def layer_tail_ok(att, resid, W1, Wo, Win=None):
-    """The encoder layer's fused forward tail (rs_layer_tail_fwd_bf16): where the fused FFN runs
-    (d = 64, F = 256, rows a multiple of 16) and the out-projection's fused LayerNorm is not
-    switched off (RSYS_UNFUSED_LN), RSYS_FWD_CHAIN not 0."""
-    return (fwd_chain_on() and ffn_supported(att, W1) and att.dtype == torch.float32 and
-            resid.dtype == torch.float32 and tuple(resid.shape) == tuple(att.shape) and resid.is_contiguous() and
-            _aligned16(resid) and
+def layer_tail_ok(rows, W1, Wo):
+    """The encoder layer's fused forward tail (rs_layer_tail_fwd_bf16) on `rows` rows: where the
+    fused FFN runs (d = 64, F = 256, rows a multiple of 16) and the out-projection's fused LayerNorm
+    is not switched off (RSYS_UNFUSED_LN), RSYS_FWD_CHAIN not 0. The attention output and the
+    residual are the encoder's own fresh fp32 allocations; layer_tail_fwd and the entry point guard
+    them."""
+    return (fwd_chain_on() and ffn_supported(rows, W1) and
             os.environ.get('RSYS_UNFUSED_LN', '0') in ('', '0') and
-            tuple(Wo.shape) == (64, 64) and _rowmajor(Wo, 64) and _aligned16(att, Wo) and
-            (Win is None or (Win.shape[0] == 192 and _rowmajor(Win, 64) and _aligned16(Win))))
+            tuple(Wo.shape) == (64, 64) and _rowmajor(Wo, 64) and _aligned16(Wo))
+
+
+def layer_tail_qkv_ok(Win):
+    """The fused tail can also emit the next layer's qkv through that layer's in-projection Win."""
+    return Win.shape[0] == 192 and _rowmajor(Win, 64) and _aligned16(Win)
 
 
 def layer_tail_fwd(att, Wo, bo, resid, g1, be1, eps1, W1, b1, W2, b2, g2, be2, eps2, p, key, site,
@@ -593,20 +604,21 @@ def seq_input_bwd_fused(dx, cat, W, L, p, key, site_a, site_b, dW, db, pos_grad)
     return out
 
 
-def seq_head_ok(segs, M, L, dcat, lin, pos, attn):
+def seq_head_ok(segs, M, L, dcat, lin, pos, attn, qkv_bf16=None):
     """The fused sequence head (rs_seq_head_fwd_bf16: gather + projection + layer 0's in-projection
     in one kernel): bf16 compute mode with the chained forward on (fwd_chain_on), bf16 qkv
     (qkv_bf16_ok), d = 64, a schema and shape the kernel takes (rs_seq_head_fwd_bf16_supported:
     single-id or mean / sum pooled segments on ordinary tables, widths multiples of 4, dcat <= 64,
     bag <= 8, the positional table within its LDS budget), both biases present, and
-    RSYS_SEQ_HEAD_FUSED not 0. The caller checks that no segment is a lazy-Adam call."""
+    RSYS_SEQ_HEAD_FUSED not 0. The caller checks that no segment is a lazy-Adam call. qkv_bf16:
+    qkv_bf16_ok's answer where the caller already has it."""
     if os.environ.get('RSYS_SEQ_HEAD_FUSED', '1') == '0' or not fwd_chain_on():
         return False
     W, Win = lin.weight, attn.in_proj_weight
     d = W.shape[0]
     if lin.bias is None or attn.in_proj_bias is None or Win is None or d != 64 or attn.embed_dim != d:
         return False
-    if not qkv_bf16_ok(L, d, attn.num_heads, M):
+    if not (qkv_bf16_ok(L, d, attn.num_heads, M) if qkv_bf16 is None else qkv_bf16):
         return False
     lib = _hip.lib()
     return (tuple(W.shape) == (64, dcat) and _rowmajor(W, dcat) and tuple(Win.shape) == (192, 64) and
