@@ -354,16 +354,40 @@ int rs_seq_mask(const int64_t* seq, int64_t ld_seq, int B, int L, int64_t pad_va
  * hd = d/H columns; out [B*L, d]; lse [B*H*L] saved for backward. Replaces the SDPA math path
  * inside nn.MultiheadAttention (SequenceEncoder.py:17-29 via TransformerEncoderLayer, K6).
  * p > 0: dropout on the attention probabilities with the rs_dropout mask of (key, site).
- * flags: RS_GEMM_BF16 -> the products on bf16 MFMA (operands rounded to bf16; softmax, dropout
- * and dS arithmetic in fp32) where the MFMA kernels apply (head_dim 16, L <= 64), else 0.
- * RS_ATTN_QKV_BF16 (with RS_GEMM_BF16, on that path only): qkv is bf16 storage and rs_attn_bwd
- * writes dqkv as bf16 (RNE); Q, K, V are MFMA operands only, so the products are unchanged. */
-#define RS_ATTN_QKV_BF16 2048
-/* zbits (optional, may be NULL; after stream so that callers of the earlier signature stay
- * valid): on the bf16 path with L <= 64 and p > 0, rs_attn_fwd stores the dropout keep decisions
- * there -- B*H*ceil(L/16)*64 uint16 words, bit 4 tk + e of word (b H + h, tq, lane) -- and
+ *
+ * Both entry points take one of four kernel routes, chosen by rs_attn_plan and nowhere else. With
+ * hd = d/H, bf = flags & RS_GEMM_BF16, and mfma_ok = hd == 16 && B*H*L*L < 2^32 (32-bit dropout
+ * element indices) && RSYS_ATTN_VALU unset or "0":
+ *   WAVE_F32   mfma_ok, L <= 64, !bf: a wave per (b, h), exact fp32 products on f32 MFMA
+ *   WAVE_BF16  mfma_ok, L <= 64, bf: the same on bf16 MFMA (operands rounded to bf16; softmax,
+ *              dropout and dS arithmetic in fp32)
+ *   LONG_BF16  mfma_ok, 64 < L <= 256, bf: a workgroup per (b, h) on bf16 MFMA
+ *   VALU       everything else, fp32 arithmetic (RS_GEMM_BF16 has no effect); K and V (backward:
+ *              and Q, dO) in dynamic LDS, (2*L*hd + L)*4 bytes forward and (4*L*hd + 3*L)*4 backward,
+ *              64 KB at the most ("exceeds LDS" otherwise)
+ * RS_ATTN_QKV_BF16 in flags (the two bf16 routes only, plan.qkv_bf16; an error elsewhere): qkv is
+ * bf16 storage and rs_attn_bwd writes dqkv as bf16 (RNE); Q, K, V are MFMA operands only, so the
+ * products are unchanged.
+ * zbits (optional, may be NULL; after stream so that callers of the earlier signature stay
+ * valid): on WAVE_BF16 with p > 0, rs_attn_fwd stores the dropout keep decisions there --
+ * plan.zbits_words = B*H*nt*64 uint16 words, bit 4 tk + e of word (b H + h, tq, lane) -- and
  * rs_attn_bwd given the same buffer reads them instead of drawing them again (identical draws).
  * Pass NULL to both, or the same buffer to both; elsewhere it is ignored. */
+#define RS_ATTN_QKV_BF16 2048
+enum { RS_ATTN_VALU = 0, RS_ATTN_WAVE_F32 = 1, RS_ATTN_WAVE_BF16 = 2, RS_ATTN_LONG_BF16 = 3 };
+typedef struct rs_attn_plan {
+  int route;            /* RS_ATTN_* */
+  int nt;               /* 16-row tiles, ceil(L/16), on the three MFMA routes, else 0 */
+  int qkv_bf16;         /* 1: the route takes bf16-stored qkv / writes bf16 dqkv (RS_ATTN_QKV_BF16) */
+  int64_t zbits_words;  /* uint16 words of keep bits the forward saves when given zbits, 0 if none */
+  int rows_ok;          /* rs_attn_rows_fwd / _bwd take this (L, head_dim) */
+} rs_attn_plan_t;
+/* The plan of an rs_attn_fwd (bwd == 0) or rs_attn_bwd (bwd != 0) call, host only (no device, no
+ * pointer is followed); `flags` without RS_ATTN_QKV_BF16 asks whether the shape could take it.
+ * Fails as the call itself would on its shape, p, head_dim, LDS need and flags; on the last two
+ * (a VALU shape beyond its LDS, RS_ATTN_QKV_BF16 off the bf16 routes) *out is written all the
+ * same, so rows_ok and qkv_bf16 answer for shapes only rs_attn_rows_* run. out may be null. */
+int rs_attn_plan(int B, int L, int d, int H, float p, int flags, int bwd, rs_attn_plan_t* out);
 int rs_attn_fwd(const float* qkv, const uint8_t* key_pad, float* out, float* lse,
                 int B, int L, int d, int H, float scale, float p, const int64_t* key, int site,
                 int flags, void* stream, uint16_t* zbits);

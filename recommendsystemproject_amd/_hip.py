@@ -49,6 +49,15 @@ class GatherLaunchPlan(C.Structure):
                [('ws_floats', i64)]
 
 
+ATTN_ROUTES = ('valu', 'wave_f32', 'wave_bf16', 'long_bf16')  # RS_ATTN_*
+
+
+class AttnPlan(C.Structure):
+    """Mirror of rs_attn_plan_t; route_name: its route in ATTN_ROUTES."""
+    _fields_ = [('route', i32), ('nt', i32), ('qkv_bf16', i32), ('zbits_words', i64), ('rows_ok', i32)]
+    route_name = property(lambda self: ATTN_ROUTES[self.route])
+
+
 class SortedCall(C.Structure):
     """Mirror of rs_sorted_call_t."""
     _fields_ = [('keys', vp), ('n', i64), ('D', i32), ('call', i32), ('p', vp), ('g', vp), ('m', vp), ('v', vp),
@@ -110,6 +119,7 @@ SIGNATURES = {
     'rs_set_deterministic': (i32, [i32]),
     'rs_gather_plan': (i32, [vp, i32, i32, i32, i32, vp, vp]),
     'rs_seq_mask': (i32, [vp, i64, i32, i32, i64, vp, vp, vp]),
+    'rs_attn_plan': (i32, [i32, i32, i32, i32, f32, i32, i32, vp]),
     'rs_attn_fwd': (i32, [vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, i32, vp, vp]),
     'rs_attn_bwd': (i32, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, i32, vp, vp]),
     'rs_attn_rows_fwd': (i32, [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, f32, vp, i32, i32, vp]),

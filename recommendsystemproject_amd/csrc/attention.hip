@@ -11,6 +11,7 @@
 //   bwd  two passes over the (query, key) pairs: lane-per-query for dQ, lane-per-key for dK/dV.
 #include <type_traits>
 
+#include "attn_rows.h"
 #include "common.h"
 #include "mfma.h"
 #include "rng.h"
@@ -1287,88 +1288,96 @@ int threads_for(int L) {
   return t > 256 ? 256 : t;
 }
 
+// dynamic LDS of the VALU kernels: K, V (and in the backward Q, dO) rows plus per-row scalars
+size_t valu_lds(int L, int hd, int bwd) {
+  return (size_t)(bwd ? 4 * L * hd + 3 * L : 2 * L * hd + L) * sizeof(float);
+}
+
+// rs_attn_plan (include/rsys_hip.h) for the entry point `fn`, which the messages name
+int attn_plan(const char* fn, int B, int L, int d, int H, float p, int flags, int bwd, rs_attn_plan_t* out) {
+  RS_CHECK_ARG(B >= 0 && L >= 1 && H >= 1 && d % H == 0, "%s: bad shape", fn);
+  RS_CHECK_ARG(p >= 0.f && p < 1.f, "%s: bad dropout p=%f", fn, p);
+  const int hd = d / H;
+  RS_CHECK_ARG(head_dim_ok(hd), "%s: head_dim %d unsupported", fn, hd);
+  const bool bf = (flags & RS_GEMM_BF16) != 0;
+  // the MFMA kernels: head_dim 16, 32-bit dropout element indices
+  const bool mfma_ok = hd == 16 && (int64_t)B * H * L * L < ((int64_t)1 << 32) && !getenv_flag("RSYS_ATTN_VALU");
+  rs_attn_plan_t pl = {};
+  pl.route = mfma_ok && L <= 64              ? (bf ? RS_ATTN_WAVE_BF16 : RS_ATTN_WAVE_F32)
+             : mfma_ok && bf && L <= 256     ? RS_ATTN_LONG_BF16
+                                             : RS_ATTN_VALU;
+  pl.nt = pl.route == RS_ATTN_VALU ? 0 : (L + 15) / 16;
+  pl.qkv_bf16 = pl.route == RS_ATTN_WAVE_BF16 || pl.route == RS_ATTN_LONG_BF16;
+  pl.zbits_words = pl.route == RS_ATTN_WAVE_BF16 && p > 0.f ? (int64_t)B * H * pl.nt * 64 : 0;
+  pl.rows_ok = attn_rows_ok(L, hd);
+  // written before the two checks below: a caller that only asks what the shape could take (rows_ok,
+  // qkv_bf16) reads it whether or not rs_attn_fwd / rs_attn_bwd themselves would run
+  if (out) *out = pl;
+  // (an empty batch launches nothing: no limit applies to it)
+  RS_CHECK_ARG(B == 0 || pl.route != RS_ATTN_VALU || valu_lds(L, hd, bwd) <= 64 * 1024,
+               "%s: L=%d hd=%d exceeds LDS", fn, L, hd);
+  RS_CHECK_ARG(B == 0 || !(flags & RS_ATTN_QKV_BF16) || pl.qkv_bf16,
+               "%s: bf16 qkv storage needs the bf16 MFMA path (RS_GEMM_BF16, head_dim 16, L <= 256, "
+               "B*H*L*L < 2^32, RSYS_ATTN_VALU off)", fn);
+  return 0;
+}
+
+// What rs_attn_fwd and rs_attn_bwd check alike, then the plan. io: out (forward) or dout (backward).
+int attn_check(const char* fn, bool pointers, const void* qkv, const void* io, int B, int L, int d, int H,
+               float p, const int64_t* key, int flags, int bwd, rs_attn_plan_t* plan) {
+  RS_CHECK_ARG(pointers, "%s: null pointer", fn);
+  RS_RET_IF(attn_plan(fn, B, L, d, H, p, flags, bwd, plan));
+  RS_CHECK_ARG(p == 0.f || key, "%s: bad dropout p=%f", fn, p);
+  RS_CHECK_ARG(B == 0 || (d % 4 == 0 && aligned16(qkv) && aligned16(io)), "%s: needs 16-byte aligned rows", fn);
+  return 0;
+}
+
 }  // namespace
 }  // namespace rs
 
 using namespace rs;
 
-// bf16 compute mode, head_dim 16, 64 < L <= 256 (fp32 or bf16 qkv): the long-history MFMA kernels
-// (L <= 64 takes the wave-per-(b, h) kernels above them in the dispatch)
-static bool long_bf16_ok(int hd, int L, int B, int H, int flags) {
-  return hd == 16 && L > 64 && L <= 256 && (flags & RS_GEMM_BF16) &&
-         (int64_t)B * H * L * L < ((int64_t)1 << 32) && !getenv_flag("RSYS_ATTN_VALU");
+extern "C" int rs_attn_plan(int B, int L, int d, int H, float p, int flags, int bwd, rs_attn_plan_t* out) {
+  return attn_plan("rs_attn_plan", B, L, d, H, p, flags, bwd, out);
 }
-
-#define RS_ATTN_DISPATCH(HDV, DROPV, KERNEL, ...)                                         \
-  switch (HDV * 2 + (DROPV ? 1 : 0)) {                                                    \
-    case 16: KERNEL<8, false><<<grid, thr, lds, st>>>(__VA_ARGS__); break;                \
-    case 17: KERNEL<8, true><<<grid, thr, lds, st>>>(__VA_ARGS__); break;                 \
-    case 32: KERNEL<16, false><<<grid, thr, lds, st>>>(__VA_ARGS__); break;               \
-    case 33: KERNEL<16, true><<<grid, thr, lds, st>>>(__VA_ARGS__); break;                \
-    case 64: KERNEL<32, false><<<grid, thr, lds, st>>>(__VA_ARGS__); break;               \
-    case 65: KERNEL<32, true><<<grid, thr, lds, st>>>(__VA_ARGS__); break;                \
-    case 128: KERNEL<64, false><<<grid, thr, lds, st>>>(__VA_ARGS__); break;              \
-    case 129: KERNEL<64, true><<<grid, thr, lds, st>>>(__VA_ARGS__); break;               \
-    default: break;                                                                       \
-  }
 
 extern "C" int rs_attn_fwd(const float* qkv, const uint8_t* key_pad, float* out, float* lse,
                            int B, int L, int d, int H, float scale, float p, const int64_t* key,
                            int site, int flags, void* stream, uint16_t* zbits) {
-  RS_CHECK_ARG(qkv && key_pad && out && lse, "rs_attn_fwd: null pointer");
-  RS_CHECK_ARG(B >= 0 && L >= 1 && H >= 1 && d % H == 0, "rs_attn_fwd: bad shape");
-  RS_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || key), "rs_attn_fwd: bad dropout p=%f", p);
-  const int hd = d / H;
-  RS_CHECK_ARG(hd == 8 || hd == 16 || hd == 32 || hd == 64, "rs_attn_fwd: head_dim %d unsupported", hd);
+  rs_attn_plan_t plan;
+  RS_RET_IF(attn_check("rs_attn_fwd", qkv && key_pad && out && lse, qkv, out, B, L, d, H, p, key, flags, 0,
+                       &plan));
   if (B == 0) return 0;
-  const size_t lds = (size_t)(2 * L * hd + L) * sizeof(float);
-  RS_CHECK_ARG(lds <= 64 * 1024 || long_bf16_ok(hd, L, B, H, flags), "rs_attn_fwd: L=%d hd=%d exceeds LDS", L, hd);
-  RS_CHECK_ARG(d % 4 == 0 && aligned16(qkv) && aligned16(out), "rs_attn_fwd: needs 16-byte aligned rows");
-  RS_CHECK_ARG(!(flags & RS_ATTN_QKV_BF16) || ((flags & RS_GEMM_BF16) && hd == 16 && L <= 256 &&
-                                                 !getenv_flag("RSYS_ATTN_VALU")),
-               "rs_attn_fwd: bf16 qkv storage needs the bf16 MFMA path (head_dim 16, L <= 256)");
   hipStream_t st = as_stream(stream);
-  if (hd == 16 && L <= 64 && (int64_t)B * H * L * L < ((int64_t)1 << 32) && !getenv_flag("RSYS_ATTN_VALU")) {
-    const int nt = (L + 15) / 16;
-    const dim3 g4(cdiv((int64_t)B * H, 4));
-    const bool bf = (flags & RS_GEMM_BF16) != 0;
-    const bool qb = (flags & RS_ATTN_QKV_BF16) != 0;
-#define RS_AF(NTV)                                                                                  \
-  if (nt == NTV) {                                                                                  \
-    if (qb && p > 0.f && zbits) attn_fwd_bf16_kernel<NTV, true, true, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site, zbits); \
-    else if (bf && !qb && p > 0.f && zbits) attn_fwd_bf16_kernel<NTV, true, false, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site, zbits); \
-    else if (qb && p > 0.f) attn_fwd_bf16_kernel<NTV, true, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
-    else if (qb) attn_fwd_bf16_kernel<NTV, false, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
-    else if (bf && p > 0.f) attn_fwd_bf16_kernel<NTV, true, false><<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
-    else if (bf) attn_fwd_bf16_kernel<NTV, false, false><<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
-    else if (p > 0.f) attn_fwd_mfma_kernel<NTV, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
-    else attn_fwd_mfma_kernel<NTV, false><<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
+  const dim3 g4(cdiv((int64_t)B * H, 4)), gbh(bh_grid(B, H));  // a wave / a workgroup per (b, h)
+  const bool drop = p > 0.f, qb = (flags & RS_ATTN_QKV_BF16) != 0;
+  const int zmode = drop + (drop && zbits);  // dropout: 0 none, 1 drawn, 2 drawn and saved to zbits
+  switch (plan.route) {
+    case RS_ATTN_WAVE_F32:
+      for_int<1, 4>(plan.nt, [&](auto nt) { for_bool(drop, [&](auto dr) {
+        attn_fwd_mfma_kernel<nt.value, dr.value>
+            <<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site);
+      }); });
+      break;
+    case RS_ATTN_WAVE_BF16:  // DROP and ZB from zmode: ZB is instantiated with DROP only
+      for_int<1, 4>(plan.nt, [&](auto nt) { for_bool(qb, [&](auto q) { for_int<0, 2>(zmode, [&](auto dm) {
+        attn_fwd_bf16_kernel<nt.value, dm.value != 0, q.value, dm.value == 2>
+            <<<g4, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site,
+                                 dm.value == 2 ? zbits : nullptr);
+      }); }); });
+      break;
+    case RS_ATTN_LONG_BF16:
+      for_int<5, 16>(plan.nt, [&](auto nt) { for_bool(qb, [&](auto q) { for_bool(drop, [&](auto dr) {
+        attn_fwd_long_bf16_kernel<nt.value, dr.value, q.value>
+            <<<gbh, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site);
+      }); }); });
+      break;
+    default:  // RS_ATTN_VALU: head_dim 8 << i
+      for_int<0, 3>(__builtin_ctz(d / H) - 3, [&](auto i) { for_bool(drop, [&](auto dr) {
+        attn_fwd_kernel<(8 << i.value), dr.value><<<gbh, threads_for(L), valu_lds(L, d / H, 0), st>>>(
+            qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site);
+      }); });
   }
-    RS_AF(1) RS_AF(2) RS_AF(3) RS_AF(4)
-#undef RS_AF
-    RS_CHECK_LAUNCH("rs_attn_fwd mfma");
-    return 0;
-  }
-  if (long_bf16_ok(hd, L, B, H, flags)) {
-    const dim3 gl(bh_grid(B, H));
-#define RS_AFL(NTV)                                                                                 \
-  if (nt == NTV) {                                                                                  \
-    if (qb && p > 0.f) attn_fwd_long_bf16_kernel<NTV, true, true><<<gl, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
-    else if (qb) attn_fwd_long_bf16_kernel<NTV, false, true><<<gl, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
-    else if (p > 0.f) attn_fwd_long_bf16_kernel<NTV, true, false><<<gl, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
-    else attn_fwd_long_bf16_kernel<NTV, false, false><<<gl, 256, 0, st>>>(qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site); \
-  }
-    const int nt = (L + 15) / 16;
-    const bool qb = (flags & RS_ATTN_QKV_BF16) != 0;
-    RS_AFL(5) RS_AFL(6) RS_AFL(7) RS_AFL(8) RS_AFL(9) RS_AFL(10) RS_AFL(11)
-    RS_AFL(12) RS_AFL(13) RS_AFL(14) RS_AFL(15) RS_AFL(16)
-#undef RS_AFL
-    RS_CHECK_LAUNCH("rs_attn_fwd long bf16");
-    return 0;
-  }
-  dim3 grid(bh_grid(B, H));
-  int thr = threads_for(L);
-  RS_ATTN_DISPATCH(hd, p > 0.f, attn_fwd_kernel, qkv, key_pad, out, lse, B, L, d, H, scale, p, key, site);
   RS_CHECK_LAUNCH("rs_attn_fwd");
   return 0;
 }
@@ -1377,63 +1386,40 @@ extern "C" int rs_attn_bwd(const float* qkv, const uint8_t* key_pad, const float
                            const float* dout, const float* lse, float* dqkv, int B, int L, int d,
                            int H, float scale, float p, const int64_t* key, int site, int flags,
                            void* stream, const uint16_t* zbits) {
-  RS_CHECK_ARG(qkv && key_pad && out && dout && lse && dqkv, "rs_attn_bwd: null pointer");
-  RS_CHECK_ARG(B >= 0 && L >= 1 && H >= 1 && d % H == 0, "rs_attn_bwd: bad shape");
-  RS_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || key), "rs_attn_bwd: bad dropout p=%f", p);
-  const int hd = d / H;
-  RS_CHECK_ARG(hd == 8 || hd == 16 || hd == 32 || hd == 64, "rs_attn_bwd: head_dim %d unsupported", hd);
+  rs_attn_plan_t plan;
+  RS_RET_IF(attn_check("rs_attn_bwd", qkv && key_pad && out && dout && lse && dqkv, qkv, dout, B, L, d, H, p, key,
+                       flags, 1, &plan));
   if (B == 0) return 0;
-  const size_t lds = (size_t)(4 * L * hd + 3 * L) * sizeof(float);
-  RS_CHECK_ARG(lds <= 64 * 1024 || long_bf16_ok(hd, L, B, H, flags), "rs_attn_bwd: L=%d hd=%d exceeds LDS", L, hd);
-  RS_CHECK_ARG(d % 4 == 0 && aligned16(qkv) && aligned16(dout), "rs_attn_bwd: needs 16-byte aligned rows");
-  RS_CHECK_ARG(!(flags & RS_ATTN_QKV_BF16) || ((flags & RS_GEMM_BF16) && hd == 16 && L <= 256 &&
-                                                 !getenv_flag("RSYS_ATTN_VALU")),
-               "rs_attn_bwd: bf16 qkv storage needs the bf16 MFMA path (head_dim 16, L <= 256)");
+  RS_CHECK_ARG(plan.route == RS_ATTN_VALU || aligned16(out), "rs_attn_bwd: needs 16-byte aligned rows");
   hipStream_t st = as_stream(stream);
-  if (hd == 16 && L <= 64 && (int64_t)B * H * L * L < ((int64_t)1 << 32) && !getenv_flag("RSYS_ATTN_VALU")) {
-    RS_CHECK_ARG(aligned16(out), "rs_attn_bwd: needs 16-byte aligned rows");
-    const int nt = (L + 15) / 16;
-    const dim3 g4(cdiv((int64_t)B * H, 4));
-    const bool bf = (flags & RS_GEMM_BF16) != 0;
-    const bool qb = (flags & RS_ATTN_QKV_BF16) != 0;
-#define RS_AB(NTV)                                                                                  \
-  if (nt == NTV) {                                                                                  \
-    if (qb && p > 0.f && zbits) attn_bwd_bf16_kernel<NTV, true, true, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site, zbits); \
-    else if (bf && !qb && p > 0.f && zbits) attn_bwd_bf16_kernel<NTV, true, false, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site, zbits); \
-    else if (qb && p > 0.f) attn_bwd_bf16_kernel<NTV, true, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
-    else if (qb) attn_bwd_bf16_kernel<NTV, false, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
-    else if (bf && p > 0.f) attn_bwd_bf16_kernel<NTV, true, false><<<g4, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
-    else if (bf) attn_bwd_bf16_kernel<NTV, false, false><<<g4, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
-    else if (p > 0.f) attn_bwd_mfma_kernel<NTV, true><<<g4, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
-    else attn_bwd_mfma_kernel<NTV, false><<<g4, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
+  const dim3 g4(cdiv((int64_t)B * H, 4)), gbh(bh_grid(B, H));
+  const bool drop = p > 0.f, qb = (flags & RS_ATTN_QKV_BF16) != 0;
+  const int zmode = drop + (drop && zbits);  // dropout: 0 none, 1 drawn again, 2 read from the forward's zbits
+  switch (plan.route) {
+    case RS_ATTN_WAVE_F32:
+      for_int<1, 4>(plan.nt, [&](auto nt) { for_bool(drop, [&](auto dr) {
+        attn_bwd_mfma_kernel<nt.value, dr.value>
+            <<<g4, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site);
+      }); });
+      break;
+    case RS_ATTN_WAVE_BF16:
+      for_int<1, 4>(plan.nt, [&](auto nt) { for_bool(qb, [&](auto q) { for_int<0, 2>(zmode, [&](auto dm) {
+        attn_bwd_bf16_kernel<nt.value, dm.value != 0, q.value, dm.value == 2><<<g4, 256, 0, st>>>(
+            qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site, dm.value == 2 ? zbits : nullptr);
+      }); }); });
+      break;
+    case RS_ATTN_LONG_BF16:
+      for_int<5, 16>(plan.nt, [&](auto nt) { for_bool(qb, [&](auto q) { for_bool(drop, [&](auto dr) {
+        attn_bwd_long1_bf16_kernel<nt.value, dr.value, q.value>
+            <<<gbh, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site);
+      }); }); });
+      break;
+    default:  // RS_ATTN_VALU: head_dim 8 << i
+      for_int<0, 3>(__builtin_ctz(d / H) - 3, [&](auto i) { for_bool(drop, [&](auto dr) {
+        attn_bwd_kernel<(8 << i.value), dr.value><<<gbh, threads_for(L), valu_lds(L, d / H, 1), st>>>(
+            qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site);
+      }); });
   }
-    RS_AB(1) RS_AB(2) RS_AB(3) RS_AB(4)
-#undef RS_AB
-    RS_CHECK_LAUNCH("rs_attn_bwd mfma");
-    return 0;
-  }
-  if (long_bf16_ok(hd, L, B, H, flags)) {
-    RS_CHECK_ARG(aligned16(out), "rs_attn_bwd: needs 16-byte aligned rows");
-    const dim3 gl(bh_grid(B, H));
-#define RS_ABL(NTV)                                                                                 \
-  if (nt == NTV) {                                                                                  \
-    if (qb && p > 0.f) attn_bwd_long1_bf16_kernel<NTV, true, true><<<gl, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
-    else if (qb) attn_bwd_long1_bf16_kernel<NTV, false, true><<<gl, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
-    else if (p > 0.f) attn_bwd_long1_bf16_kernel<NTV, true, false><<<gl, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
-    else attn_bwd_long1_bf16_kernel<NTV, false, false><<<gl, 256, 0, st>>>(qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale, p, key, site); \
-  }
-    const int nt = (L + 15) / 16;
-    const bool qb = (flags & RS_ATTN_QKV_BF16) != 0;
-    RS_ABL(5) RS_ABL(6) RS_ABL(7) RS_ABL(8) RS_ABL(9) RS_ABL(10) RS_ABL(11)
-    RS_ABL(12) RS_ABL(13) RS_ABL(14) RS_ABL(15) RS_ABL(16)
-#undef RS_ABL
-    RS_CHECK_LAUNCH("rs_attn_bwd long bf16");
-    return 0;
-  }
-  dim3 grid(bh_grid(B, H));
-  int thr = threads_for(L);
-  RS_ATTN_DISPATCH(hd, p > 0.f, attn_bwd_kernel, qkv, key_pad, out, dout, lse, dqkv, B, L, d, H, scale,
-                   p, key, site);
   RS_CHECK_LAUNCH("rs_attn_bwd");
   return 0;
 }

@@ -14,14 +14,13 @@
 // bf16 where the MFMA kernels round them (q, k, v, dO, P∘Z, dS), products accumulate in fp32.
 #include <type_traits>
 
+#include "attn_rows.h"
 #include "common.h"
 #include "mfma.h"
 #include "rng.h"
 
 namespace rs {
 namespace {
-
-constexpr int kMaxChunks = 4;  // L <= 256
 
 __device__ __forceinline__ float r16(float x) { return (float)(__bf16)x; }
 
@@ -257,31 +256,23 @@ __global__ __launch_bounds__(256) void attn_rows_bwd_kernel(
 
 using namespace rs;
 
-#define RS_ROWS_DISPATCH(KERNEL, ...)                                                             \
-  do {                                                                                            \
-    const dim3 grid(cdiv((int64_t)B * H, 4));                                                     \
-    const int key_ = (hd == 8 ? 0 : hd == 16 ? 1 : hd == 32 ? 2 : 3) * 8 + (p > 0.f) * 4 + bf * 2 + qb; \
-    switch (key_) {                                                                               \
-      RS_ROWS_CASE(KERNEL, 8, 0, __VA_ARGS__) RS_ROWS_CASE(KERNEL, 16, 1, __VA_ARGS__)            \
-      RS_ROWS_CASE(KERNEL, 32, 2, __VA_ARGS__) RS_ROWS_CASE(KERNEL, 64, 3, __VA_ARGS__)           \
-      default: break;                                                                             \
-    }                                                                                             \
-  } while (0)
-#define RS_ROWS_CASE(KERNEL, HDV, HI, ...)                                                        \
-  case HI * 8 + 0: KERNEL<HDV, false, false, false><<<grid, 256, 0, st>>>(__VA_ARGS__); break;    \
-  case HI * 8 + 2: KERNEL<HDV, false, true, false><<<grid, 256, 0, st>>>(__VA_ARGS__); break;     \
-  case HI * 8 + 3: KERNEL<HDV, false, true, true><<<grid, 256, 0, st>>>(__VA_ARGS__); break;      \
-  case HI * 8 + 4: KERNEL<HDV, true, false, false><<<grid, 256, 0, st>>>(__VA_ARGS__); break;     \
-  case HI * 8 + 6: KERNEL<HDV, true, true, false><<<grid, 256, 0, st>>>(__VA_ARGS__); break;      \
-  case HI * 8 + 7: KERNEL<HDV, true, true, true><<<grid, 256, 0, st>>>(__VA_ARGS__); break;
+// launch(HD, DROP, BF, QB tags) for this call's head_dim, dropout and precision: fp32, bf16-rounded
+// operands, or those read from bf16 storage (QB is instantiated with BF only: rows_check)
+template <typename F>
+static void rows_dispatch(int hd, float p, int flags, F&& launch) {
+  const int prec = !(flags & RS_GEMM_BF16) ? 0 : !(flags & RS_ATTN_QKV_BF16) ? 1 : 2;
+  for_int<0, 3>(__builtin_ctz(hd) - 3, [&](auto i) { for_bool(p > 0.f, [&](auto drop) { for_int<0, 2>(prec, [&](auto pr) {
+    launch(std::integral_constant<int, (8 << i.value)>{}, drop, std::bool_constant<pr.value != 0>{},
+           std::bool_constant<pr.value == 2>{});
+  }); }); });
+}
 
 static int rows_check(const void* qkv, int B, int L, int d, int H, float p, const int64_t* key,
                       int flags, const char* fn) {
   RS_CHECK_ARG(B >= 0 && L >= 1 && H >= 1 && d % H == 0, "%s: bad shape", fn);
   RS_CHECK_ARG(L <= 64 * kMaxChunks, "%s: L=%d > %d", fn, L, 64 * kMaxChunks);
   RS_CHECK_ARG(p >= 0.f && p < 1.f && (p == 0.f || key), "%s: bad dropout p=%f", fn, p);
-  const int hd = d / H;
-  RS_CHECK_ARG(hd == 8 || hd == 16 || hd == 32 || hd == 64, "%s: head_dim %d unsupported", fn, hd);
+  RS_CHECK_ARG(head_dim_ok(d / H), "%s: head_dim %d unsupported", fn, d / H);
   RS_CHECK_ARG(!(flags & RS_ATTN_QKV_BF16) || (flags & RS_GEMM_BF16),
                "%s: bf16 qkv storage needs RS_GEMM_BF16", fn);
   RS_CHECK_ARG(aligned16(qkv) && d % 8 == 0, "%s: needs 16-byte aligned rows", fn);
@@ -296,8 +287,10 @@ extern "C" int rs_attn_rows_fwd(const float* qkv, const uint8_t* key_pad, const 
   RS_CHECK_ARG(aligned16(out), "rs_attn_rows_fwd: out must be 16-byte aligned");
   if (B == 0) return 0;
   hipStream_t st = as_stream(stream);
-  const int hd = d / H, bf = (flags & RS_GEMM_BF16) != 0, qb = (flags & RS_ATTN_QKV_BF16) != 0;
-  RS_ROWS_DISPATCH(attn_rows_fwd_kernel, qkv, key_pad, last, out, lse, B, L, d, H, scale, p, key, site);
+  rows_dispatch(d / H, p, flags, [&](auto hd, auto drop, auto bf, auto qb) {
+    attn_rows_fwd_kernel<hd.value, drop.value, bf.value, qb.value>
+        <<<cdiv((int64_t)B * H, 4), 256, 0, st>>>(qkv, key_pad, last, out, lse, B, L, d, H, scale, p, key, site);
+  });
   RS_CHECK_LAUNCH("rs_attn_rows_fwd");
   return 0;
 }
@@ -311,9 +304,11 @@ extern "C" int rs_attn_rows_bwd(const float* qkv, const uint8_t* key_pad, const 
   RS_CHECK_ARG(aligned16(dout) && aligned16(dqkv), "rs_attn_rows_bwd: needs 16-byte aligned rows");
   if (B == 0) return 0;
   hipStream_t st = as_stream(stream);
-  const int hd = d / H, bf = (flags & RS_GEMM_BF16) != 0, qb = (flags & RS_ATTN_QKV_BF16) != 0;
-  RS_ROWS_DISPATCH(attn_rows_bwd_kernel, qkv, key_pad, last, dout, lse, dqkv, B, L, d, H, scale, p,
-                   key, site);
+  rows_dispatch(d / H, p, flags, [&](auto hd, auto drop, auto bf, auto qb) {
+    attn_rows_bwd_kernel<hd.value, drop.value, bf.value, qb.value>
+        <<<cdiv((int64_t)B * H, 4), 256, 0, st>>>(qkv, key_pad, last, dout, lse, dqkv, B, L, d, H, scale, p, key,
+                                                  site);
+  });
   RS_CHECK_LAUNCH("rs_attn_rows_bwd");
   return 0;
 }

@@ -5,6 +5,8 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "../../include/rsys_hip.h"
 
 namespace rs {
@@ -90,6 +92,21 @@ inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s);
 inline bool getenv_flag(const char* name) {
   const char* v = getenv(name);
   return v && v[0] && !(v[0] == '0' && v[1] == 0);
+}
+// Run-time value -> template argument: for_int<Lo, Hi>(v, f) calls f(std::integral_constant<int, v>{})
+// when Lo <= v <= Hi (else nothing); for_bool calls f with std::true_type or std::false_type.
+// Inside f, `tag.value` is the constant (a template argument).
+template <int Lo, int Hi, typename F>
+inline void for_int(int v, F&& f) {
+  if constexpr (Lo <= Hi) {
+    if (v == Lo) f(std::integral_constant<int, Lo>{});
+    else for_int<Lo + 1, Hi>(v, f);
+  }
+}
+template <typename F>
+inline void for_bool(bool v, F&& f) {
+  if (v) f(std::true_type{});
+  else f(std::false_type{});
 }
 inline int cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }

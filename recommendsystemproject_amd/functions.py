@@ -466,12 +466,15 @@ def plan_encoder(enc, segs, tables, B, L) -> EncoderPlan:
     proc = enc.feature_embedder
     layers = list(enc.transformer_backbone.layers)
     n, M, d = len(layers), B * L, proc.target_dim
-    qkv_bf16 = ops.qkv_bf16_ok(L, d, enc.n_head, M)
+    # one look at the attention planner, not strict: the pruned last layer runs attn_rows_* only, at
+    # shapes (head_dim 64, L = 200) the full attention kernels do not take
+    att = ops.attn_plan(B, L, d, enc.n_head, 0.0, precision.gemm_flags(), strict=False) if n else None
+    qkv_bf16 = ops.qkv_bf16_ok(L, d, enc.n_head, M, plan=att)
     lin = proc.feature_projection[0]
     fused = (n > 0 and not any(hasattr(t, '_rs_lazy') for t in tables) and
              ops.seq_head_ok(segs, M, L, sum(s.dim for s in segs), lin, proc.pos_emb.weight, layers[0].self_attn,
                              qkv_bf16=qkv_bf16))
-    prune = prune_last_layer() and L <= 256
+    prune = prune_last_layer() and n > 0 and bool(att.rows_ok)
     plans = []
     for i, lyr in enumerate(layers):
         rows = prune and i == n - 1

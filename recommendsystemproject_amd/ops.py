@@ -361,35 +361,44 @@ def gather_bwd(segs, rows, dout):
 STREAM_BF16_MIN_ROWS = 32768  # gemm_stream.hip kSmallM: the bf16-storage GEMM instances are big-M only
 
 
-def qkv_bf16_ok(L, d, H, M):
-    """Store the packed qkv (and dqkv) as bf16: bf16 compute mode on the bf16 MFMA attention
-    path (head_dim 16, L <= 256), where Q, K, V are only MFMA operands (RS_ATTN_QKV_BF16), for
-    token counts M the bf16-storage streaming GEMMs cover (M >= 32768, a multiple of 16)."""
-    return (precision.compute_dtype() == 'bf16' and d // H == 16 and L <= 256 and
-            M >= STREAM_BF16_MIN_ROWS and M % 16 == 0 and
-            not os.environ.get('RSYS_ATTN_VALU') and not os.environ.get('RSYS_QKV_FP32'))
+def attn_plan(B, L, d, H, p, flags, bwd=False, strict=True):
+    """rs_attn_plan (host only): the _hip.AttnPlan of an attn_fwd / attn_bwd call with these flags --
+    its kernel route (.route_name, one of _hip.ATTN_ROUTES), whether that route takes bf16-stored qkv,
+    the keep-bit words the forward saves, and whether attn_rows_* take the shape. strict: raise where
+    attn_fwd / attn_bwd would. Not strict, for a caller that only asks what the shape could take
+    (plan_encoder: a pruned layer never calls attn_fwd): no error, the plan as far as the library
+    filled it -- whole but for a VALU shape beyond its LDS, all zero for a shape it refuses outright.
+    Not through call(): a plan is no launch, and call() is where launches are timed and recorded."""
+    plan, lib = _hip.AttnPlan(), _hip.lib()
+    if lib.rs_attn_plan(B, L, d, H, float(p), flags, int(bwd), _hip.C.byref(plan)) != 0 and strict:
+        raise _hip.HipError(f"rs_attn_plan failed: {lib.rs_last_error().decode(errors='replace')}")
+    return plan
+
+
+def qkv_bf16_ok(L, d, H, M, plan=None):
+    """Store the packed qkv (and dqkv) as bf16: bf16 compute mode on an attention route that takes
+    it (attn_plan: Q, K, V are only MFMA operands there, RS_ATTN_QKV_BF16), for token counts M the
+    bf16-storage streaming GEMMs cover (M >= 32768, a multiple of 16). plan: the caller's
+    attn_plan(M // L, L, d, H, 0, gemm_flags, strict=False) where it already has it."""
+    if not (precision.compute_dtype() == 'bf16' and M >= STREAM_BF16_MIN_ROWS and M % 16 == 0 and
+            not os.environ.get('RSYS_QKV_FP32')):
+        return False
+    if plan is None:
+        plan = attn_plan(M // L, L, d, H, 0.0, precision.gemm_flags(), strict=False)
+    return bool(plan.qkv_bf16)
 
 
 def _attn_flags(qkv):
     return precision.gemm_flags() | (_hip.RS_ATTN_QKV_BF16 if qkv.dtype == torch.bfloat16 else 0)
 
 
-def _zbits_words(B, L, d, H, p, flags):
-    """uint16 words of rs_attn_fwd's saved dropout keep bits (include/rsys_hip.h): the bf16 MFMA
-    path with L <= 64 and p > 0 (the dispatch condition of attention.hip), else 0."""
-    if not (p > 0 and flags & _hip.RS_GEMM_BF16 and d // H == 16 and L <= 64 and B * H * L * L < 2 ** 32
-            and not os.environ.get('RSYS_ATTN_VALU')):
-        return 0
-    return B * H * ((L + 15) // 16) * 64
-
-
 def attn_fwd(qkv, key_pad, B, L, d, H, p=0.0, key=None, site=0):
     """-> out [B*L, d], lse [B*H*L]. Where the kernel saves its dropout keep bits for the backward
-    (_zbits_words), they live in lse's storage past its B*H*L floats, so whoever keeps lse for
+    (attn_plan's zbits_words), they live in lse's storage past its B*H*L floats, so whoever keeps lse for
     attn_bwd keeps them too; an lse without that tail makes attn_bwd draw them again."""
     out = torch.empty(B * L, d, device=qkv.device, dtype=torch.float32)
     flags = _attn_flags(qkv)
-    n, zw = B * H * L, _zbits_words(B, L, d, H, p, flags)
+    n, zw = B * H * L, attn_plan(B, L, d, H, p, flags).zbits_words
     if zw:
         buf = torch.empty(n + (zw + 1) // 2 + 4, device=qkv.device, dtype=torch.float32)
         lse, zb = buf[:n], _zbits_ptr(buf, n)
@@ -408,7 +417,7 @@ def attn_bwd(qkv, key_pad, out, dout, lse, B, L, d, H, p=0.0, key=None, site=0):
     """dqkv has qkv's storage dtype (bf16 with RS_ATTN_QKV_BF16)."""
     dqkv = torch.empty(B * L, 3 * d, device=qkv.device, dtype=qkv.dtype)
     flags = _attn_flags(qkv)
-    n, zw = B * H * L, _zbits_words(B, L, d, H, p, flags)
+    n, zw = B * H * L, attn_plan(B, L, d, H, p, flags, bwd=True).zbits_words
     zb = None
     if zw and lse.storage_offset() == 0 and lse.numel() == n and \
             lse.untyped_storage().nbytes() == 4 * (n + (zw + 1) // 2 + 4):

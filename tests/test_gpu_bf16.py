@@ -476,7 +476,7 @@ def test_bf16_attention_saved_keep_bits(L, bf16_mode):
     dout = rnd(B * L, d, seed=16)
     q32 = rnd(B * L, 3 * d, seed=15)
     for q in (q32, q32.to(torch.bfloat16)):
-        assert ops._zbits_words(B, L, d, H, p, ops._attn_flags(q)) > 0
+        assert ops.attn_plan(B, L, d, H, p, ops._attn_flags(q)).zbits_words > 0
         o, lse = ops.attn_fwd(q, key_pad, B, L, d, H, p, key, 7)
         assert lse.numel() == B * H * L and lse.untyped_storage().nbytes() > 4 * lse.numel()
         g_bits = ops.attn_bwd(q, key_pad, o, dout, lse, B, L, d, H, p, key, 7)
@@ -484,6 +484,37 @@ def test_bf16_attention_saved_keep_bits(L, bf16_mode):
         assert torch.equal(g_bits, g_hash)
         o2, _ = ops.attn_fwd(q, key_pad, B, L, d, H, p, key, 8)  # another site: other draws
         assert not torch.equal(o, o2)
+
+
+@pytest.mark.parametrize('L,route', [(64, 'wave_bf16'), (65, 'long_bf16'), (244, 'long_bf16')])
+def test_bf16_attention_route_boundaries(L, route, bf16_mode):
+    """The edges of the planned routes (ops.attn_plan): L = 64 the wave-per-head kernels on full
+    tiles, L = 65 the smallest long shape (one key in its last tile), L = 244 the largest the fp32
+    reference backward takes. fp32- and bf16-stored qkv agree with the fp32-mode kernels on the same
+    (upcast) qkv, same dropout masks, within test_bf16_attention_dropout_matches_fp32_masks' bounds."""
+    B, d, H, p = 3, 64, 4, 0.2
+    lens = torch.randint(1, L + 1, (B,), generator=torch.Generator().manual_seed(L))
+    seq = (torch.arange(L)[None, :] < lens[:, None]).long().to(DEV)
+    key_pad, _ = ops.seq_mask(seq, 0)
+    key = torch.tensor([31, 8], dtype=torch.int64, device=DEV)
+    dout = rnd(B * L, d, seed=18)
+    q32 = rnd(B * L, 3 * d, seed=17)
+    for q in (q32, q32.to(torch.bfloat16)):
+        for bwd in (False, True):
+            assert ops.attn_plan(B, L, d, H, p, ops._attn_flags(q), bwd).route_name == route
+        o16, l16 = ops.attn_fwd(q, key_pad, B, L, d, H, p, key, 6)
+        g16 = ops.attn_bwd(q, key_pad, o16, dout, l16, B, L, d, H, p, key, 6)
+        assert g16.dtype == q.dtype
+        precision.set_compute_dtype('fp32')
+        try:
+            o32, l32 = ops.attn_fwd(q.float(), key_pad, B, L, d, H, p, key, 6)
+            g32 = ops.attn_bwd(q.float(), key_pad, o32, dout, l32, B, L, d, H, p, key, 6)
+        finally:
+            precision.set_compute_dtype('bf16')
+        eo, so = (o16 - o32).abs().max().item(), o32.abs().max().item()
+        eg, sg = (g16.float() - g32).abs().max().item(), g32.abs().max().item()
+        print(f'L={L} {q.dtype}: out err {eo:.3e} of max {so:.3e}; dqkv err {eg:.3e} of max {sg:.3e}')
+        assert eo < 2e-2 * so and eg < 3e-2 * sg
 
 
 def _ce_ref(U, I, ids, H, T, gout=1.0):

@@ -26,6 +26,7 @@ def main():
     key_pad, _ = ops.seq_mask(seq, 0)
     key = torch.tensor([5, 1], dtype=torch.int64, device=dev)
     dout = torch.randn(B * L, d, device=dev)
+    print('route', ops.attn_plan(B, L, d, H, p, ops._attn_flags(qkv)).route_name, flush=True)
     for _ in range(3):
         out, lse = ops.attn_fwd(qkv, key_pad, B, L, d, H, p, key, 3)
         ops.attn_bwd(qkv, key_pad, out, dout, lse, B, L, d, H, p, key, 3)

@@ -40,7 +40,8 @@ def main():
         ops.attn_bwd(qkv, key_pad, out, dout, lse, B, L, d, H, p, key, 3)
     ev[2].record()
     torch.cuda.synchronize()
-    print(json.dumps({'attn_fwd_us': round(ev[0].elapsed_time(ev[1]) / n * 1e3, 1),
+    print(json.dumps({'route': ops.attn_plan(B, L, d, H, p, ops._attn_flags(qkv)).route_name,
+                      'attn_fwd_us': round(ev[0].elapsed_time(ev[1]) / n * 1e3, 1),
                       'attn_bwd_us': round(ev[1].elapsed_time(ev[2]) / n * 1e3, 1)}))
 
 
