@@ -699,6 +699,38 @@ int rs_target_rank_e4m3(const float* U, int64_t ldu, int B, const void* items, i
                         const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
                         const int32_t* hist_idx, int64_t num_users, int splits, void* ws, int64_t ws_bytes,
                         int32_t* out_rank, void* stream);
+/* Catalog filters for the same two (in stock, this locale, a tombstone for a deleted item): an
+ * index holds num_filters >= 0 allow-lists as packed bits, filter_bits [num_filters, filter_ld]
+ * uint32 words with column c of filter f at bit c & 31 of word c >> 5 (filter_ld >= ceil(N / 32);
+ * bits at or past N are not read). rs_pack_mask makes them on the device from a byte mask
+ * [F, N] (row stride ld bytes, nonzero = allowed; bits [F, ld_bits] words, the unused high bits of
+ * a row's last word zero; any 1 <= N < 2^31, F >= 1). Each user b names one filter,
+ * f = filter_ids[b * fid_stride]; f outside [0, num_filters) means no filter for that user, as a
+ * user id outside [0, num_users) means no history. A column outside the user's filter scores -inf
+ * exactly as a history column does, and the two exclusions combine by union. Everything else is
+ * rs_fused_topk's and rs_target_rank's definition on the masked scores: values descending, ties
+ * by the lower column, masked columns only when fewer than K unmasked exist (lowest column first,
+ * value -inf), a masked target behind every unmasked column, out_rank[b] < K exactly when
+ * rs_fused_topk_filtered with the same filters returns the target. item_kind: 0 fp32, 1 bf16,
+ * 2 e4m3 (ldi in bytes; item_exp in [-40, 40], ignored otherwise). NULL filter_ids or num_filters
+ * == 0: exactly the unfiltered call (the same kernels). Every other argument, check and message,
+ * the splits and the workspace as rs_fused_topk / rs_target_rank (the split count is the same;
+ * a filtered call moves the split boundaries onto filter words where every split keeps K columns,
+ * which changes no result). */
+int rs_pack_mask(const uint8_t* mask, int64_t ld, int F, int64_t N, uint32_t* bits, int64_t ld_bits,
+                 void* stream);
+int rs_fused_topk_filtered(const float* U, int64_t ldu, int B, const void* items, int item_kind, int item_exp,
+                           int64_t ldi, int64_t N, int D, int K, const int64_t* user_ids, int64_t uid_stride,
+                           const int64_t* hist_off, const int32_t* hist_idx, int64_t num_users,
+                           const int32_t* filter_ids, int64_t fid_stride, const uint32_t* filter_bits,
+                           int64_t filter_ld, int num_filters, int splits, void* ws, int64_t ws_bytes,
+                           int32_t* out_idx, float* out_val, int64_t ld_out, void* stream);
+int rs_target_rank_filtered(const float* U, int64_t ldu, int B, const void* items, int item_kind, int item_exp,
+                            int64_t ldi, int64_t N, int D, const int32_t* target_col, int64_t tc_stride,
+                            const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
+                            const int32_t* hist_idx, int64_t num_users, const int32_t* filter_ids,
+                            int64_t fid_stride, const uint32_t* filter_bits, int64_t filter_ld, int num_filters,
+                            int splits, void* ws, int64_t ws_bytes, int32_t* out_rank, void* stream);
 
 /* ---------------------------------------------------------------- clip + Adam
  * Flat multi-tensor path over a contiguous fp32 range (all parameters packed in one buffer).

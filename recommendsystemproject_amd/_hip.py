@@ -181,6 +181,11 @@ SIGNATURES = {
                                  vp, vp, i64, vp]),
     'rs_target_rank_e4m3': (i32, [vp, i64, i32, vp, i32, i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, i32, vp,
                                   i64, vp, vp]),
+    'rs_pack_mask': (i32, [vp, i64, i32, i64, vp, i64, vp]),
+    'rs_fused_topk_filtered': (i32, [vp, i64, i32, vp, i32, i32, i64, i64, i32, i32, vp, i64, vp, vp, i64, vp, i64,
+                                     vp, i64, i32, i32, vp, i64, vp, vp, i64, vp]),
+    'rs_target_rank_filtered': (i32, [vp, i64, i32, vp, i32, i32, i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp,
+                                      i64, vp, i64, i32, i32, vp, i64, vp, vp]),
     'rs_collate_ragged': (i32, [vp, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
     'rs_catalog_gather': (i32, [vp, i32, i32, i64, i32, i64, vp, i32, i32, i64, vp, i64, vp, vp]),
     'rs_sqnorm_ws_bytes': (i64, [i64]),

@@ -23,6 +23,18 @@
 // them (ties by candidate position = column order). K <= 32: 4 waves x 32 users per workgroup,
 // lists of 80; K <= 256: one wave of 32 users, lists of 352 (rows x capacity x 8 B beside the item
 // tiles in 160 KiB).
+//
+// Catalog filters (rs_fused_topk_filtered / rs_target_rank_filtered; the FILT instances, the others
+// compile without any of it): a user may name one of F packed allow-lists (rs_pack_mask: bit c & 31
+// of word c >> 5 of row f is column c). A column outside the user's list scores -inf exactly as a
+// history column does. The host starts the splits of a filtered call on filter words wherever that
+// leaves every split its K columns (filter_split_words); a block's 32 columns are then one word of
+// the user's row, fetched by the lane, and the masked scores are set to -inf BEFORE the block
+// maximum: a block with nothing allowed is skipped like a block below the threshold, and a
+// selective filter does not send every finite score down the serial admission path. Splits that
+// must start inside a word (few columns a split: small catalogs only) test the column's bit on
+// admission instead, as history does. The rank kernel funnel-shifts two words there; it takes
+// the sign-trick path only for blocks whose 32 bits are set for every user of the wave.
 #include "retrieve_tile.h"
 
 namespace rs {
@@ -38,6 +50,54 @@ __device__ __forceinline__ uint32_t ft_order_key(float v) {
 __device__ __forceinline__ float ft_key_value(uint32_t k) {
   const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
   return __uint_as_float(u);
+}
+
+// Catalog filters: a user's packed row as its first word's index in `bits` (one register; -1:
+// unfiltered) and the 32 bits of the block of columns [colbase, colbase + 32), bit i = column
+// colbase + i is allowed. Columns at or past N read as 0.
+struct FtFilter {
+  const int32_t* ids;  // [B] with stride, null: nobody is filtered
+  int64_t id_stride;
+  const uint32_t* bits;  // [num_filters][ld] words, num_filters * ld < 2^31
+  int64_t ld;
+  int num_filters;
+  int words;        // ceil(N / 32)
+  int split_words;  // != 0: split s starts at column 32 * (s * words / splits) (one word a block)
+};
+
+__device__ __forceinline__ int ft_filter_row(const FtFilter& f, int o, bool o_ok) {
+  if (!o_ok || !f.ids || !f.bits) return -1;
+  const int id = f.ids[(int64_t)o * f.id_stride];
+  return id >= 0 && id < f.num_filters ? id * (int)f.ld : -1;
+}
+
+__device__ __forceinline__ uint32_t ft_filter_word(const FtFilter& f, int row, int colbase) {
+  if (row < 0) return 0xffffffffu;
+  const int w = colbase >> 5, sh = colbase & 31;
+  if (w >= f.words) return 0u;
+  const uint32_t lo = f.bits[row + w];
+  if (sh == 0) return lo;  // uniform over the workgroup: every block of a word-aligned split
+  const uint32_t hi = w + 1 < f.words ? f.bits[row + w + 1] : 0u;
+  return __builtin_amdgcn_alignbit(hi, lo, sh);
+}
+
+// the 16 bits of a block's word that belong to lane half h, bit e = element e (column colbase +
+// 8 (e >> 2) + 4 h + (e & 3)): nibbles 2 q + h of the word
+__device__ __forceinline__ uint32_t ft_elem_bits(uint32_t word, int h) {
+  const uint32_t v = word >> (4 * h);
+  return (v & 0xfu) | ((v >> 4) & 0xf0u) | ((v >> 8) & 0xf00u) | ((v >> 12) & 0xf000u);
+}
+
+// the columns [begin, end) of a split
+__device__ __forceinline__ void ft_split_range(int split, int splits, int split_cols, int N, int words,
+                                               int split_words, int& begin, int& end) {
+  if (split_words) {
+    begin = 32 * (int)((int64_t)split * words / splits);
+    end = split == splits - 1 ? N : 32 * (int)((int64_t)(split + 1) * words / splits);
+  } else {
+    begin = split * split_cols;
+    end = split == splits - 1 ? N : begin + split_cols;
+  }
 }
 
 struct FtArgs {
@@ -57,6 +117,7 @@ struct FtArgs {
   int32_t* out_idx;  // [B][ld_out], this split's candidates at split * K
   float* out_val;    // nullable
   int64_t ld_out;
+  FtFilter f;  // the FILT instances only
 };
 
 // the best K of list L (n entries) to L[0 .. K), sorted descending; thr = value of the K-th
@@ -94,9 +155,11 @@ __device__ __forceinline__ void ft_prune_row(unsigned long long* L, int* cnt, fl
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
 }
 
-template <int DP, FtElem EK, int KB>
+template <int DP, FtElem EK, int KB, bool FILT>
 __global__ __launch_bounds__((FtCfg<DP, EK, KB>::NT)) void fused_topk_kernel(FtArgs a) {
-  using Cfg = FtCfg<DP, EK, KB>;
+  // the one unfiltered instance that fills all 512 registers takes 32-item tiles when filtered
+  // (half the staging registers) rather than spill to scratch
+  using Cfg = FtCfg<DP, EK, KB, FILT && DP == 256 && EK == kBF16 && KB == 1>;
   using E = FtStore<EK>;
   constexpr int ROWS = Cfg::ROWS, CAP = Cfg::CAP, TI = Cfg::TI, NB = Cfg::NB;
   constexpr int SL = Cfg::SL, ESZ = Cfg::ESZ;
@@ -104,6 +167,7 @@ __global__ __launch_bounds__((FtCfg<DP, EK, KB>::NT)) void fused_topk_kernel(FtA
   __shared__ unsigned long long lists[ROWS * CAP];
   __shared__ int s_cnt[ROWS];
   __shared__ float s_thr[ROWS];
+  __shared__ int s_frow[FILT ? ROWS : 1];  // FILT: the users' filter rows (a register fewer to hold)
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = lane & 31, h = lane >> 5;
@@ -113,8 +177,12 @@ __global__ __launch_bounds__((FtCfg<DP, EK, KB>::NT)) void fused_topk_kernel(FtA
   const int lrow = wave * 32 + c;  // this lane's user: list row and, + rt * ROWS, batch row
   const int o = rt * ROWS + lrow;
   const bool o_ok = o < a.B;
-  const int c_begin = split * a.split_cols;
-  const int c_end = split == a.splits - 1 ? a.N : c_begin + a.split_cols;
+  int c_begin = split * a.split_cols;
+  int c_end = split == a.splits - 1 ? a.N : c_begin + a.split_cols;
+  if constexpr (FILT) {
+    ft_split_range(split, a.splits, a.split_cols, a.N, a.f.words, a.f.split_words, c_begin, c_end);
+    if (h == 0) s_frow[lrow] = ft_filter_row(a.f, o, o_ok);
+  }
   const int ntiles = (c_end - c_begin + TI - 1) / TI;
 
   // NaN threshold: "never held K entries", every score is admitted (!(s <= NaN)); rows past B
@@ -161,6 +229,10 @@ __global__ __launch_bounds__((FtCfg<DP, EK, KB>::NT)) void fused_topk_kernel(FtA
             if (a.hist_idx[mid] < col) lo = mid + 1; else hi = mid;
           }
           if (lo < h_hi && a.hist_idx[lo] == col) s = -INFINITY;
+          if constexpr (FILT) {  // splits that start inside a filter word: the bit on admission
+            const int frow = s_frow[lrow];
+            if (!a.f.split_words && frow >= 0 && !((a.f.bits[frow + (col >> 5)] >> (col & 31)) & 1u)) s = -INFINITY;
+          }
           if (!(s <= thr)) {
             const int slot = atomicAdd(&s_cnt[lrow], 1);
             if (slot < CAP)
@@ -186,6 +258,16 @@ __global__ __launch_bounds__((FtCfg<DP, EK, KB>::NT)) void fused_topk_kernel(FtA
     ft_mfma<DP, EK, NB>(tiles[t & 1], PT, D, c, h, uf, acc);
 #pragma unroll
     for (int ib = 0; ib < NB; ++ib) {
+      if constexpr (FILT) {
+        // word-aligned splits: the block's filter word before its maximum
+        const int frow = s_frow[lrow], fwi = (c_begin + t * TI + ib * 32) >> 5;
+        const uint32_t fw = !a.f.split_words || frow < 0 ? 0xffffffffu : fwi < a.f.words ? a.f.bits[frow + fwi] : 0u;
+        if (__any(fw != 0xffffffffu)) {
+          const uint32_t v = fw >> (4 * h);  // element e: bit 8 (e >> 2) + (e & 3)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[ib][e] = (v >> (8 * (e >> 2) + (e & 3))) & 1u ? acc[ib][e] : -INFINITY;
+        }
+      }
       float m = acc[ib][0];
 #pragma unroll
       for (int e = 1; e < 16; ++e) m = fmaxf(m, acc[ib][e]);
@@ -269,9 +351,10 @@ struct TrArgs {
   int64_t num_users;
   int splits, split_cols, nrt;
   int32_t* out;  // one split: the ranks [B]; else this split's partial counts at split * B
+  FtFilter f;    // the FILT instances only
 };
 
-template <int DP, FtElem EK>
+template <int DP, FtElem EK, bool FILT>
 __global__ __launch_bounds__((FtCfg<DP, EK, 0>::NT)) void target_rank_kernel(TrArgs a) {
   using Cfg = FtCfg<DP, EK, 0>;
   using E = FtStore<EK>;
@@ -285,8 +368,13 @@ __global__ __launch_bounds__((FtCfg<DP, EK, 0>::NT)) void target_rank_kernel(TrA
   const int PT = ft_pitch<EK>(D);
   const int o = rt * ROWS + wave * 32 + c;  // this lane's user
   const bool o_ok = o < a.B;
-  const int c_begin = split * a.split_cols;
-  const int c_end = split == a.splits - 1 ? a.N : c_begin + a.split_cols;
+  int c_begin = split * a.split_cols;
+  int c_end = split == a.splits - 1 ? a.N : c_begin + a.split_cols;
+  int frow = -1;  // the user's filter row
+  if constexpr (FILT) {
+    ft_split_range(split, a.splits, a.split_cols, a.N, a.f.words, a.f.split_words, c_begin, c_end);
+    frow = ft_filter_row(a.f, o, o_ok);
+  }
   const int ntiles = (c_end - c_begin + TI - 1) / TI;
 
   int tcol = -1;  // the target column, -1: not in the catalog (or a row past B)
@@ -366,6 +454,9 @@ __global__ __launch_bounds__((FtCfg<DP, EK, 0>::NT)) void target_rank_kernel(TrA
       if (lo < h_hi && a.hist_idx[lo] == tcol) ts = -INFINITY;
     }
   }
+  if constexpr (FILT) {  // and by its own filter bit
+    if (frow >= 0 && tcol >= 0 && !((a.f.bits[frow + (tcol >> 5)] >> (tcol & 31)) & 1u)) ts = -INFINITY;
+  }
   int hnext = hp < h_hi ? a.hist_idx[hp] : kTrNoCol;
   // s > ts  <=>  s >= ts_up, the next float above ts (ts = +-0: the smallest subnormal)
   const uint32_t tb = __float_as_uint(ts);
@@ -377,7 +468,9 @@ __global__ __launch_bounds__((FtCfg<DP, EK, 0>::NT)) void target_rank_kernel(TrA
     if (colbase >= c_end) return;
     const bool t_in = (unsigned)(tcol - colbase) < 32u;
     const bool h_in = hnext - colbase < 32;
-    if (colbase <= c_end - 32 && !__any(t_in || h_in)) {
+    uint32_t fw = 0xffffffffu;  // the block's filter bits: the fast path needs all 32 of every user
+    if constexpr (FILT) fw = ft_filter_word(a.f, frow, colbase);
+    if (colbase <= c_end - 32 && !__any(t_in || h_in || fw != 0xffffffffu)) {
       // s >= thr <=> the sign of s - thr is clear (f32 subnormals are kept, so the difference of
       // unequal floats is never zero; x - x = +0): the 16 sign bits go through one funnel shift
       // each into w, two VALU operations per score and no compare
@@ -388,13 +481,14 @@ __global__ __launch_bounds__((FtCfg<DP, EK, 0>::NT)) void target_rank_kernel(TrA
       cnt += 16 - __popc(w);
       return;
     }
-    uint32_t hmask = 0;  // bit e: element e is a history column of this user
+    uint32_t hmask = 0;  // bit e: element e is a masked (history or filtered) column of this user
     while (hnext - colbase < 32) {
       const int d = hnext - colbase;  // >= 0: the cursor never lags a block
       if (((d >> 2) & 1) == h) hmask |= 1u << (4 * (d >> 3) + (d & 3));
       ++hp;
       hnext = hp < h_hi ? a.hist_idx[hp] : kTrNoCol;
     }
+    if constexpr (FILT) hmask |= ~ft_elem_bits(fw, h) & 0xffffu;  // a filtered column counts as history does
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int col = colbase + 8 * (e >> 2) + 4 * h + (e & 3);
@@ -475,33 +569,57 @@ __global__ __launch_bounds__(256) void rescore_kernel(const float* __restrict__ 
 
 inline int ft_rows(int K) { return K <= kFtSmallK ? 128 : 32; }
 
-template <int DP, FtElem EK>
+template <int DP, FtElem EK, bool FILT>
 int ft_launch_k(const FtArgs& a, int grid, hipStream_t st) {
   if (a.K <= kFtSmallK)
-    fused_topk_kernel<DP, EK, 0><<<grid, FtCfg<DP, EK, 0>::NT, 0, st>>>(a);
+    fused_topk_kernel<DP, EK, 0, FILT><<<grid, FtCfg<DP, EK, 0>::NT, 0, st>>>(a);
   else
-    fused_topk_kernel<DP, EK, 1><<<grid, FtCfg<DP, EK, 1>::NT, 0, st>>>(a);
+    fused_topk_kernel<DP, EK, 1, FILT><<<grid, FtCfg<DP, EK, 1>::NT, 0, st>>>(a);
   RS_CHECK_LAUNCH("rs_fused_topk");
   return 0;
 }
 
+template <FtElem EK, bool FILT>
+int ft_launch_d(const FtArgs& a, int grid, hipStream_t st) {
+  if (a.D <= 64) return ft_launch_k<64, EK, FILT>(a, grid, st);
+  if (a.D <= 128) return ft_launch_k<128, EK, FILT>(a, grid, st);
+  return ft_launch_k<256, EK, FILT>(a, grid, st);
+}
+
+// the FILT instances only for a call that names filters: every other call runs the kernels it ran
+// before filters existed
 template <FtElem EK>
 int ft_launch(const FtArgs& a, int grid, hipStream_t st) {
-  if (a.D <= 64) return ft_launch_k<64, EK>(a, grid, st);
-  if (a.D <= 128) return ft_launch_k<128, EK>(a, grid, st);
-  return ft_launch_k<256, EK>(a, grid, st);
+  return a.f.ids ? ft_launch_d<EK, true>(a, grid, st) : ft_launch_d<EK, false>(a, grid, st);
+}
+
+template <FtElem EK, bool FILT>
+int tr_launch_d(const TrArgs& a, int grid, hipStream_t st) {
+  if (a.D <= 64)
+    target_rank_kernel<64, EK, FILT><<<grid, FtCfg<64, EK, 0>::NT, 0, st>>>(a);
+  else if (a.D <= 128)
+    target_rank_kernel<128, EK, FILT><<<grid, FtCfg<128, EK, 0>::NT, 0, st>>>(a);
+  else
+    target_rank_kernel<256, EK, FILT><<<grid, FtCfg<256, EK, 0>::NT, 0, st>>>(a);
+  RS_CHECK_LAUNCH("rs_target_rank");
+  return 0;
 }
 
 template <FtElem EK>
 int tr_launch(const TrArgs& a, int grid, hipStream_t st) {
-  if (a.D <= 64)
-    target_rank_kernel<64, EK><<<grid, FtCfg<64, EK, 0>::NT, 0, st>>>(a);
-  else if (a.D <= 128)
-    target_rank_kernel<128, EK><<<grid, FtCfg<128, EK, 0>::NT, 0, st>>>(a);
-  else
-    target_rank_kernel<256, EK><<<grid, FtCfg<256, EK, 0>::NT, 0, st>>>(a);
-  RS_CHECK_LAUNCH("rs_target_rank");
-  return 0;
+  return a.f.ids ? tr_launch_d<EK, true>(a, grid, st) : tr_launch_d<EK, false>(a, grid, st);
+}
+
+// rs_pack_mask: a wave per 64 columns of one filter, one ballot, two words
+__global__ __launch_bounds__(256) void pack_mask_kernel(const uint8_t* __restrict__ mask, int64_t ld, int64_t N,
+                                                        int64_t blocks_per_row, uint32_t* __restrict__ bits,
+                                                        int64_t ld_bits) {
+  const int64_t f = blockIdx.x / blocks_per_row;
+  const int64_t c = (blockIdx.x % blocks_per_row) * 256 + threadIdx.x;
+  const unsigned long long b = __ballot(c < N && mask[f * ld + c] != 0);
+  const int lane = threadIdx.x & 63;
+  // lanes 0 and 32 hold the first column of a word; columns at or past N contributed 0 bits
+  if ((lane & 31) == 0 && c < N) bits[f * ld_bits + (c >> 5)] = (uint32_t)(b >> lane);
 }
 
 }  // namespace
@@ -528,12 +646,39 @@ extern "C" int64_t rs_fused_topk_ws_bytes(int B, int64_t N, int D, int K, int sp
   return (int64_t)B * splits * K * 8;  // values fp32 + columns int32, [B][splits * K] each
 }
 
-// rs_fused_topk and rs_fused_topk_e4m3: ek the item element, ldi in elements (e4m3: bytes)
+// The filter arguments of the two _filtered calls, checked (after N) and made the kernels' FtFilter:
+// no ids or no filters is the unfiltered call.
+static int filter_args(const char* name, const int32_t* filter_ids, int64_t fid_stride, const uint32_t* filter_bits,
+                       int64_t filter_ld, int num_filters, int64_t N, FtFilter* f) {
+  *f = FtFilter{};
+  RS_CHECK_ARG(num_filters >= 0, "%s: num_filters = %d < 0", name, num_filters);
+  if (!filter_ids || num_filters == 0) return 0;
+  const int64_t words = (N + 31) / 32;
+  RS_CHECK_ARG(filter_bits, "%s: null filter_bits with num_filters = %d", name, num_filters);
+  RS_CHECK_ARG(filter_ld >= words, "%s: filter_ld = %lld, a row of N = %lld columns has %lld words (rs_pack_mask)",
+               name, (long long)filter_ld, (long long)N, (long long)words);
+  RS_CHECK_ARG(filter_ld * num_filters < (int64_t)1 << 31, "%s: %d filters of %lld words: 2^31 words or more", name,
+               num_filters, (long long)filter_ld);
+  f->ids = filter_ids; f->id_stride = fid_stride; f->bits = filter_bits; f->ld = filter_ld;
+  f->num_filters = num_filters; f->words = (int)words;
+  return 0;
+}
+
+// Filtered calls start every split on a filter word (one word per 32-column block) where that
+// leaves each split `min_cols` columns: split s covers the words [s W / splits, (s + 1) W / splits),
+// the last one the catalog's tail, so a split has at least 32 (W / splits) - 31 columns.
+static int filter_split_words(const FtFilter& f, int splits, int min_cols) {
+  return f.ids && 32 * (int64_t)(f.words / splits) - 31 >= min_cols ? 1 : 0;
+}
+
+// rs_fused_topk, rs_fused_topk_e4m3 and rs_fused_topk_filtered: ek the item element, ldi in
+// elements (e4m3: bytes)
 static int fused_topk_any(const float* U, int64_t ldu, int B, const void* items, FtElem ek, int item_exp,
                           int64_t ldi, int64_t N, int D, int K, const int64_t* user_ids, int64_t uid_stride,
                           const int64_t* hist_off, const int32_t* hist_idx, int64_t num_users, int splits,
                           void* ws, int64_t ws_bytes, int32_t* out_idx, float* out_val, int64_t ld_out,
-                          void* stream) {
+                          void* stream, const int32_t* filter_ids = nullptr, int64_t fid_stride = 0,
+                          const uint32_t* filter_bits = nullptr, int64_t filter_ld = 0, int num_filters = 0) {
   const int ld_mult = ek == kF32 ? 4 : ek == kBF16 ? 8 : 16;  // a row stride of whole 16-byte chunks
   RS_CHECK_ARG(U && items && out_idx && B >= 0, "rs_fused_topk: null U / items / out_idx or B < 0");
   RS_CHECK_ARG(D >= 16 && D <= 256 && D % 16 == 0,
@@ -543,6 +688,9 @@ static int fused_topk_any(const float* U, int64_t ldu, int B, const void* items,
   RS_CHECK_ARG(ldu >= D && ldu % 4 == 0 && ldi >= D && ldi % ld_mult == 0 && aligned16(U) &&
                    aligned16(items) && ld_out >= K,
                "rs_fused_topk: rows of U and items must be 16-byte aligned, ld >= D, ld_out >= K");
+  FtFilter flt;
+  RS_RET_IF(filter_args("rs_fused_topk_filtered", filter_ids, fid_stride, filter_bits, filter_ld, num_filters, N,
+                        &flt));
   if (splits <= 0) splits = rs_fused_topk_splits(B, N, D, K);
   RS_CHECK_ARG(N / splits >= K, "rs_fused_topk: splits = %d leaves a split fewer than K = %d columns", splits,
                K);
@@ -557,6 +705,7 @@ static int fused_topk_any(const float* U, int64_t ldu, int B, const void* items,
   a.user_ids = user_ids; a.uid_stride = uid_stride; a.hist_off = hist_off; a.hist_idx = hist_idx;
   a.num_users = num_users;
   a.splits = splits; a.split_cols = (int)(N / splits); a.nrt = cdiv(B, ft_rows(K));
+  a.f = flt; a.f.split_words = filter_split_words(flt, splits, K);
   const int64_t ldw = (int64_t)splits * K;
   float* ws_val = static_cast<float*>(ws);
   int32_t* ws_idx = reinterpret_cast<int32_t*>(ws_val + (int64_t)B * ldw);
@@ -595,6 +744,38 @@ extern "C" int rs_fused_topk_e4m3(const float* U, int64_t ldu, int B, const void
                         hist_idx, num_users, splits, ws, ws_bytes, out_idx, out_val, ld_out, stream);
 }
 
+extern "C" int rs_fused_topk_filtered(const float* U, int64_t ldu, int B, const void* items, int item_kind,
+                                      int item_exp, int64_t ldi, int64_t N, int D, int K, const int64_t* user_ids,
+                                      int64_t uid_stride, const int64_t* hist_off, const int32_t* hist_idx,
+                                      int64_t num_users, const int32_t* filter_ids, int64_t fid_stride,
+                                      const uint32_t* filter_bits, int64_t filter_ld, int num_filters, int splits,
+                                      void* ws, int64_t ws_bytes, int32_t* out_idx, float* out_val, int64_t ld_out,
+                                      void* stream) {
+  RS_CHECK_ARG(item_kind >= 0 && item_kind <= 2,
+               "rs_fused_topk_filtered: item_kind = %d (0 fp32, 1 bf16, 2 e4m3)", item_kind);
+  RS_CHECK_ARG(item_kind != 2 || (item_exp >= -kE4m3MaxExp && item_exp <= kE4m3MaxExp),
+               "rs_fused_topk_filtered: item_exp = %d outside [-40, 40]", item_exp);
+  return fused_topk_any(U, ldu, B, items, item_kind == 0 ? kF32 : item_kind == 1 ? kBF16 : kE4M3,
+                        item_kind == 2 ? item_exp : 0, ldi, N, D, K, user_ids, uid_stride, hist_off, hist_idx,
+                        num_users, splits, ws, ws_bytes, out_idx, out_val, ld_out, stream, filter_ids, fid_stride,
+                        filter_bits, filter_ld, num_filters);
+}
+
+extern "C" int rs_pack_mask(const uint8_t* mask, int64_t ld, int F, int64_t N, uint32_t* bits, int64_t ld_bits,
+                            void* stream) {
+  RS_CHECK_ARG(mask && bits && F >= 1, "rs_pack_mask: null mask / bits or F = %d < 1", F);
+  RS_CHECK_ARG(N >= 1 && N < (int64_t)1 << 31, "rs_pack_mask: bad sizes (N=%lld; 1 <= N < 2^31)", (long long)N);
+  RS_CHECK_ARG(ld >= N && ld_bits >= (N + 31) / 32,
+               "rs_pack_mask: ld = %lld < N = %lld or ld_bits = %lld < %lld words", (long long)ld, (long long)N,
+               (long long)ld_bits, (long long)((N + 31) / 32));
+  const int64_t blocks_per_row = (N + 255) / 256;
+  RS_CHECK_ARG(blocks_per_row * F < (int64_t)1 << 31, "rs_pack_mask: too many filters (F=%d N=%lld)", F, (long long)N);
+  pack_mask_kernel<<<(int)(blocks_per_row * F), 256, 0, as_stream(stream)>>>(mask, ld, N, blocks_per_row, bits,
+                                                                            ld_bits);
+  RS_CHECK_LAUNCH("rs_pack_mask");
+  return 0;
+}
+
 extern "C" int rs_target_rank_splits(int B, int64_t N, int D) {
   (void)D;
   if (B < 1 || N < 1) return 1;
@@ -614,12 +795,15 @@ extern "C" int64_t rs_target_rank_ws_bytes(int B, int64_t N, int D, int splits) 
   return n < 16 ? 16 : n;
 }
 
-// rs_target_rank and rs_target_rank_e4m3: ek the item element, ldi in elements (e4m3: bytes)
+// rs_target_rank, rs_target_rank_e4m3 and rs_target_rank_filtered: ek the item element, ldi in
+// elements (e4m3: bytes)
 static int target_rank_any(const float* U, int64_t ldu, int B, const void* items, FtElem ek, int item_exp,
                            int64_t ldi, int64_t N, int D, const int32_t* target_col, int64_t tc_stride,
                            const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off,
                            const int32_t* hist_idx, int64_t num_users, int splits, void* ws, int64_t ws_bytes,
-                           int32_t* out_rank, void* stream) {
+                           int32_t* out_rank, void* stream, const int32_t* filter_ids = nullptr,
+                           int64_t fid_stride = 0, const uint32_t* filter_bits = nullptr, int64_t filter_ld = 0,
+                           int num_filters = 0) {
   const int ld_mult = ek == kF32 ? 4 : ek == kBF16 ? 8 : 16;  // a row stride of whole 16-byte chunks
   RS_CHECK_ARG(U && items && target_col && out_rank && B >= 0,
                "rs_target_rank: null U / items / target_col / out_rank or B < 0");
@@ -629,6 +813,9 @@ static int target_rank_any(const float* U, int64_t ldu, int B, const void* items
   RS_CHECK_ARG(ldu >= D && ldu % 4 == 0 && ldi >= D && ldi % ld_mult == 0 && aligned16(U) &&
                    aligned16(items),
                "rs_target_rank: rows of U and items must be 16-byte aligned, ld >= D");
+  FtFilter flt;
+  RS_RET_IF(filter_args("rs_target_rank_filtered", filter_ids, fid_stride, filter_bits, filter_ld, num_filters, N,
+                        &flt));
   if (splits <= 0) splits = rs_target_rank_splits(B, N, D);
   RS_CHECK_ARG(splits <= N, "rs_target_rank: splits = %d leaves a split no column (N=%lld)", splits, (long long)N);
   const int64_t need = splits > 1 ? rs_target_rank_ws_bytes(B, N, D, splits) : 0;
@@ -643,6 +830,7 @@ static int target_rank_any(const float* U, int64_t ldu, int B, const void* items
   a.user_ids = user_ids; a.uid_stride = uid_stride; a.hist_off = hist_off; a.hist_idx = hist_idx;
   a.num_users = num_users;
   a.splits = splits; a.split_cols = (int)(N / splits); a.nrt = cdiv(B, 128);
+  a.f = flt; a.f.split_words = filter_split_words(flt, splits, 1);
   a.out = splits == 1 ? out_rank : static_cast<int32_t*>(ws);
   const int64_t grid = (int64_t)a.nrt * splits;
   RS_CHECK_ARG(grid < (int64_t)1 << 31, "rs_target_rank: grid too large");
@@ -675,6 +863,23 @@ extern "C" int rs_target_rank_e4m3(const float* U, int64_t ldu, int B, const voi
                "rs_target_rank_e4m3: item_exp = %d outside [-40, 40]", item_exp);
   return target_rank_any(U, ldu, B, items, kE4M3, item_exp, ldi, N, D, target_col, tc_stride, user_ids,
                          uid_stride, hist_off, hist_idx, num_users, splits, ws, ws_bytes, out_rank, stream);
+}
+
+extern "C" int rs_target_rank_filtered(const float* U, int64_t ldu, int B, const void* items, int item_kind,
+                                       int item_exp, int64_t ldi, int64_t N, int D, const int32_t* target_col,
+                                       int64_t tc_stride, const int64_t* user_ids, int64_t uid_stride,
+                                       const int64_t* hist_off, const int32_t* hist_idx, int64_t num_users,
+                                       const int32_t* filter_ids, int64_t fid_stride, const uint32_t* filter_bits,
+                                       int64_t filter_ld, int num_filters, int splits, void* ws, int64_t ws_bytes,
+                                       int32_t* out_rank, void* stream) {
+  RS_CHECK_ARG(item_kind >= 0 && item_kind <= 2,
+               "rs_target_rank_filtered: item_kind = %d (0 fp32, 1 bf16, 2 e4m3)", item_kind);
+  RS_CHECK_ARG(item_kind != 2 || (item_exp >= -kE4m3MaxExp && item_exp <= kE4m3MaxExp),
+               "rs_target_rank_filtered: item_exp = %d outside [-40, 40]", item_exp);
+  return target_rank_any(U, ldu, B, items, item_kind == 0 ? kF32 : item_kind == 1 ? kBF16 : kE4M3,
+                         item_kind == 2 ? item_exp : 0, ldi, N, D, target_col, tc_stride, user_ids, uid_stride,
+                         hist_off, hist_idx, num_users, splits, ws, ws_bytes, out_rank, stream, filter_ids,
+                         fid_stride, filter_bits, filter_ld, num_filters);
 }
 
 // ---- the e4m3 index format (e4m3.h): scale exponent, host encoder, device quantiser

@@ -30,7 +30,8 @@ __device__ __forceinline__ constexpr int ft_pitch(int D) {
 }
 
 // DP: the embedding width the registers and LDS are sized for (D <= DP); KB: the K bucket
-template <int DP, FtElem EK, int KB>
+// NARROW: 32-item tiles whatever fits (a quarter to a half of the staging registers)
+template <int DP, FtElem EK, int KB, bool NARROW = false>
 struct FtCfg {
   static constexpr int NW = KB == 0 ? 4 : 1;        // waves per workgroup
   static constexpr int NT = 64 * NW;
@@ -39,7 +40,7 @@ struct FtCfg {
   static constexpr int ESZ = EK == kF32 ? 4 : EK == kBF16 ? 2 : 1;
   static constexpr int PTMAX = EK == kF32 ? DP + 4 : EK == kBF16 ? DP + 8 : DP + 16;  // largest pitch, D <= DP
   // items per tile: two LDS buffers within 72 KB (one wave stages at most 64 rows)
-  static constexpr int TI = (KB == 0 && 2 * 128 * PTMAX * ESZ <= 72 * 1024) ? 128
+  static constexpr int TI = NARROW ? 32 : (KB == 0 && 2 * 128 * PTMAX * ESZ <= 72 * 1024) ? 128
                             : (2 * 64 * PTMAX * ESZ <= 72 * 1024) ? 64 : 32;
   static constexpr int NB = TI / 32;                // 32-item blocks per tile
   static constexpr int CPR = DP * ESZ / 16;         // 16-byte chunks per item row at D = DP

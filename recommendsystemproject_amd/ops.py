@@ -745,13 +745,59 @@ def quantize_e4m3(rows, exp=None):
     return q, int(exp)
 
 
-def fused_topk(U, items, K, user_ids=None, history=None, splits=0, item_exp=None):
+def pack_mask(mask):
+    """Allow-lists as the packed words the filtered retrieval kernels read (rs_pack_mask): mask
+    [F, N] or [N], bool or uint8 on the device, nonzero = the column is allowed ->
+    uint32 [F, ceil(N / 32)], column c at bit c & 31 of word c >> 5, the last word's unused high
+    bits zero."""
+    _hip.require_device(mask)
+    m = mask.detach()
+    if m.dim() == 1:
+        m = m.view(1, -1)
+    if m.dim() != 2 or m.dtype not in (torch.bool, torch.uint8):
+        raise ValueError(f'pack_mask: a bool or uint8 mask [F, N] or [N], got {m.dtype} {tuple(mask.shape)}')
+    if m.dtype == torch.bool:
+        m = m.view(torch.uint8) if m.is_contiguous() else m.to(torch.uint8)
+    F, N = int(m.shape[0]), int(m.shape[1])
+    if F < 1 or N < 1:
+        raise ValueError(f'pack_mask: needs at least one filter and one column, got {tuple(mask.shape)}')
+    if m.stride(1) != 1 or (F > 1 and m.stride(0) < N):
+        m = m.contiguous()
+    W = (N + 31) // 32
+    bits = torch.empty(F, W, device=m.device, dtype=torch.uint32)
+    call('rs_pack_mask', P(m), int(m.stride(0)) if F > 1 else N, F, N, P(bits), W, stream())
+    return bits
+
+
+def _filter_args(name, filter_ids, filters, B, N):
+    """(ids int32 [B], stride, bits, ld, F) of a filtered call: filters = pack_mask's words."""
+    if filters is None:
+        raise ValueError(f'{name}: filter_ids given without filters (pack_mask)')
+    for t in (filter_ids, filters):
+        _hip.require_device(t)
+    if filters.dim() != 2 or filters.dtype != torch.uint32 or filters.shape[1] < (N + 31) // 32:
+        raise ValueError(f'{name}: filters must be uint32 [F, >= {(N + 31) // 32}] (pack_mask), got '
+                         f'{filters.dtype} {tuple(filters.shape)}')
+    if filters.stride(1) != 1:
+        filters = filters.contiguous()
+    fid = filter_ids.reshape(-1)
+    if fid.numel() != B:
+        raise ValueError(f'{name}: {fid.numel()} filter ids for {B} users')
+    if fid.dtype != torch.int32:
+        fid = fid.long().clamp(-1, int(filters.shape[0])).int()  # out of range either way: unfiltered
+    return fid, int(fid.stride(0)), filters, int(filters.stride(0)), int(filters.shape[0])
+
+
+def fused_topk(U, items, K, user_ids=None, history=None, splits=0, item_exp=None, filter_ids=None, filters=None):
     """The K best catalog columns of every user by dot product, and their scores, without the
     [B, N] score matrix (rs_fused_topk). U [B, D] fp32; items [N, D] fp32, bf16 or float8_e4m3fn
     with item_exp, the index scale exponent (the dtype picks the kernel; rs_fused_topk_e4m3);
     history = (off, idx, num_users) with each user's columns SORTED ascending
     (retrieval.sorted_history_csr), applied when user_ids is given. -> (idx int32 [B, K],
-    val fp32 [B, K]), values descending, ties by the lower column. No CPU fallback."""
+    val fp32 [B, K]), values descending, ties by the lower column. filter_ids integer [B] with
+    filters = pack_mask(allow-lists [F, N]) (rs_fused_topk_filtered): user b sees only the columns
+    of filter filter_ids[b], the others score -inf as history columns do; an id outside [0, F)
+    leaves that user unfiltered. No CPU fallback."""
     use_hist = history is not None and user_ids is not None
     for t in (U, items) + ((user_ids,) + tuple(history[:2]) if use_hist else ()):
         _hip.require_device(t)
@@ -775,18 +821,27 @@ def fused_topk(U, items, K, user_ids=None, history=None, splits=0, item_exp=None
         uid = user_ids if user_ids.dtype == torch.int64 else user_ids.long()
         us = int(uid.stride(0))
         off, hidx, nu = history
-    call('rs_fused_topk' + suffix, P(U), int(U.stride(0)), B, P(items), kind,
-         int(items.stride(0)), N, D, int(K), P(uid), us, P(off), P(hidx), int(nu), int(splits), P(w), int(nbytes),
-         P(idx), P(val), K, stream())
+    if filter_ids is None:
+        call('rs_fused_topk' + suffix, P(U), int(U.stride(0)), B, P(items), kind,
+             int(items.stride(0)), N, D, int(K), P(uid), us, P(off), P(hidx), int(nu), int(splits), P(w), int(nbytes),
+             P(idx), P(val), K, stream())
+        return idx, val
+    fid, fs, bits, fld, F = _filter_args('fused_topk', filter_ids, filters, B, N)
+    call('rs_fused_topk_filtered', P(U), int(U.stride(0)), B, P(items), 2 if suffix else kind, kind if suffix else 0,
+         int(items.stride(0)), N, D, int(K), P(uid), us, P(off), P(hidx), int(nu), P(fid), fs, P(bits), fld, F,
+         int(splits), P(w), int(nbytes), P(idx), P(val), K, stream())
     return idx, val
 
 
-def target_rank(U, items, target_cols, user_ids=None, history=None, splits=0, item_exp=None):
+def target_rank(U, items, target_cols, user_ids=None, history=None, splits=0, item_exp=None, filter_ids=None,
+                filters=None):
     """For every user the 0-based position of catalog column target_cols[b] in fused_topk's order
     over the whole catalog (rs_target_rank): the number of columns with a higher masked score, or
     an equal one and a lower column. rank < K exactly when the target is among the user's top K,
     for any K. U, items, item_exp, user_ids and history as fused_topk's (history applies to the target too);
-    target_cols integer [B], a column outside [0, N) ranks -1. -> int32 [B]. No CPU fallback."""
+    target_cols integer [B], a column outside [0, N) ranks -1. filter_ids / filters as fused_topk's
+    (rs_target_rank_filtered): a target outside the user's filter ranks behind every allowed
+    column. -> int32 [B]. No CPU fallback."""
     use_hist = history is not None and user_ids is not None
     for t in (U, items, target_cols) + ((user_ids,) + tuple(history[:2]) if use_hist else ()):
         _hip.require_device(t)
@@ -817,9 +872,15 @@ def target_rank(U, items, target_cols, user_ids=None, history=None, splits=0, it
         uid = user_ids if user_ids.dtype == torch.int64 else user_ids.long()
         us = int(uid.stride(0))
         off, hidx, nu = history
-    call('rs_target_rank' + suffix, P(U), int(U.stride(0)), B, P(items), kind,
-         int(items.stride(0)), N, D, P(tc), int(tc.stride(0)), P(uid), us, P(off), P(hidx), int(nu),
-         int(splits), P(w), int(nbytes), P(out), stream())
+    if filter_ids is None:
+        call('rs_target_rank' + suffix, P(U), int(U.stride(0)), B, P(items), kind,
+             int(items.stride(0)), N, D, P(tc), int(tc.stride(0)), P(uid), us, P(off), P(hidx), int(nu),
+             int(splits), P(w), int(nbytes), P(out), stream())
+        return out
+    fid, fs, bits, fld, F = _filter_args('target_rank', filter_ids, filters, B, N)
+    call('rs_target_rank_filtered', P(U), int(U.stride(0)), B, P(items), 2 if suffix else kind, kind if suffix else 0,
+         int(items.stride(0)), N, D, P(tc), int(tc.stride(0)), P(uid), us, P(off), P(hidx), int(nu), P(fid), fs,
+         P(bits), fld, F, int(splits), P(w), int(nbytes), P(out), stream())
     return out
 
 

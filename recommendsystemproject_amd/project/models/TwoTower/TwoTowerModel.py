@@ -179,19 +179,20 @@ class TwoTowerModel(nn.Module):
         finally:
             self.train(was_training)
 
-    def recommend(self, user_inputs, index, k, user_ids=None, oversample=1):
+    def recommend(self, user_inputs, index, k, user_ids=None, oversample=1, filters=None):
         """The k best items of `index` (retrieval.ItemIndex) for each user of `user_inputs` (a
         user-tower batch): the user tower alone in eval mode under no_grad, then index.search.
-        -> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first."""
+        -> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first. filters:
+        one of the index's catalog filters (ItemIndex.set_filters) by id or name, or ids [B]."""
         user_emb = self._serving_user_emb(user_inputs)
-        return index.search(user_emb, k, user_ids=user_ids, oversample=oversample)
+        return index.search(user_emb, k, user_ids=user_ids, oversample=oversample, filters=filters)
 
-    def rank_targets(self, user_inputs, index, target_item_ids, user_ids=None):
+    def rank_targets(self, user_inputs, index, target_item_ids, user_ids=None, filters=None):
         """The full-catalog rank of each user's target item in `index` (retrieval.ItemIndex.rank):
         the user tower alone in eval mode under no_grad, then index.rank. -> int32 [B], 0 = best,
-        -1 for an item the catalog does not hold."""
+        -1 for an item the catalog does not hold. filters as recommend's."""
         user_emb = self._serving_user_emb(user_inputs)
-        return index.rank(user_emb, target_item_ids, user_ids=user_ids)
+        return index.rank(user_emb, target_item_ids, user_ids=user_ids, filters=filters)
 
     _NAN_MSG = {1: 'Found NaN in User Embedding', 2: 'Found NaN in Item Embedding',
                 4: 'Found NaN in Hard Negative Embedding'}

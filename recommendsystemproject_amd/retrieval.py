@@ -15,6 +15,17 @@ ordering over the WHOLE catalog does each user's held-out item stand (rs_target_
 per user; training_utils.ranking_metrics turns it into Recall / NDCG at any k, MRR, mean rank).
 
     ranks = model.rank_targets(batch['user_tower'], index, target_item_ids, user_ids=uids)
+
+Catalog filters restrict a request to a subset of the catalog inside the same two kernels (in
+stock, this locale, a tombstone for a deleted item): an allow-list per filter, packed to one bit
+a column on the device (rs_pack_mask), and one filter per user and request. A column outside the
+user's filter scores -inf exactly as a history column does (the two combine by union), so search
+still returns k items when fewer than k are allowed (the masked ones last, at -inf) and rank < k
+exactly when search(k) with the same filter returns the item.
+
+    index.set_filters({'in_stock': stock_mask, 'kids': index.mask_of(kids_item_ids)})
+    item_ids, scores, cols = model.recommend(batch['user_tower'], index, k=20, filters='in_stock')
+    item_ids, scores, cols = index.search(user_emb, 20, filters=per_user_filter_ids)   # < 0: none
 """
 from __future__ import annotations
 
@@ -72,6 +83,8 @@ class ItemIndex:
         self._dtype = dtype
         self._history = None
         self._by_id = None  # (sorted ids, their columns), built by the first columns_of
+        self._filters = None        # packed allow-lists, uint32 [F, ceil(N / 32)] (ops.pack_mask)
+        self._filter_names = None   # name -> filter id, for filters given as a dict
 
     @classmethod
     def from_embeddings(cls, embs, item_ids=None, dtype='fp32', keep_fp32=True):
@@ -145,30 +158,112 @@ class ItemIndex:
         if user_history is not None:
             self._history = sorted_history_csr(user_history, self.item_ids.cpu().numpy(), self.item_ids.device)
 
-    def search(self, user_emb, k, user_ids=None, oversample=1):
-        """-> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first."""
+    def set_filters(self, masks):
+        """Catalog filters: each an allow-list over the catalog's columns, in column order. masks:
+        a bool / uint8 tensor or array [F, N] or [N] (nonzero = allowed; filter ids 0 .. F - 1),
+        or a dict name -> [N] mask (ids in the dict's order, names usable in search / rank); None
+        clears them. Only the packed words stay, on the index's device (N / 8 bytes a filter;
+        packed there by rs_pack_mask, or on the host for an index that lives on the host, which
+        cannot search).
+        search / rank then take filters=. A filter is applied inside the fused kernels, which still
+        sweep the whole catalog: for a filter that keeps a very small part of it, a compact
+        sub-index (from_embeddings on the allowed rows) reads far less. To combine filters, AND
+        their masks here."""
+        if masks is None:
+            self._filters = self._filter_names = None
+            return
+        names = None
+        if isinstance(masks, dict):
+            if not masks:
+                raise ValueError('set_filters: an empty dict of filters (None clears them)')
+            names = {name: i for i, name in enumerate(masks)}
+            rows = [torch.as_tensor(np.asarray(m) if not torch.is_tensor(m) else m).reshape(-1) for m in masks.values()]
+            for name, r in zip(masks, rows):
+                if r.numel() != len(self):
+                    raise ValueError(f'set_filters: filter {name!r} has {r.numel()} columns, the catalog {len(self)}')
+            m = torch.stack([r.to(self.item_ids.device) != 0 for r in rows])
+        else:
+            m = torch.as_tensor(np.asarray(masks) if not torch.is_tensor(masks) else masks)
+            if m.dim() == 1:
+                m = m.view(1, -1)
+            if m.dim() != 2 or m.shape[0] < 1 or m.shape[1] != len(self):
+                raise ValueError(f'set_filters: masks [F, N] or [N] with N = {len(self)} catalog columns, '
+                                 f'got {tuple(m.shape)}')
+            if m.dtype not in (torch.bool, torch.uint8):
+                raise ValueError(f'set_filters: bool or uint8 masks, got {m.dtype}')
+            m = m.to(self.item_ids.device)
+        if m.is_cuda:
+            self._filters = ops.pack_mask(m)
+        else:  # a host index: the same words (little-endian bit order), no device to pack on
+            b = np.packbits(m.numpy() != 0, axis=1, bitorder='little')
+            b = np.pad(b, ((0, 0), (0, -b.shape[1] % 4)))
+            self._filters = torch.from_numpy(np.ascontiguousarray(b).view('<u4').astype(np.int64)).to(torch.uint32)
+        self._filter_names = names
+
+    @property
+    def num_filters(self):
+        return 0 if self._filters is None else int(self._filters.shape[0])
+
+    def mask_of(self, item_ids):
+        """bool [N] on the index's device: True at every catalog column whose item id is listed
+        (every column of an id the catalog holds twice; an id it does not hold marks nothing), so
+        an allow-list of ids becomes a filter: set_filters(index.mask_of(ids))."""
+        q = torch.as_tensor(item_ids).reshape(-1).long().to(self.item_ids.device)
+        return torch.isin(self.item_ids, q)
+
+    def _filter_ids(self, filters, B, device):
+        """search / rank's `filters` -> int32 [B] on the device (negative: unfiltered), or None."""
+        if filters is None:
+            return None
+        if self._filters is None:
+            raise ValueError('filters given, but the index has none: call set_filters first')
+        if not fused_supported(self.dim):
+            raise ValueError(f'catalog filters run in the fused kernels only: embedding widths that are a multiple '
+                             f'of 16 in [16, 256], got {self.dim}')
+        if torch.is_tensor(filters) or isinstance(filters, (np.ndarray, list, tuple)):
+            f = torch.as_tensor(filters)
+            if f.is_floating_point() or f.dtype == torch.bool or f.numel() != B:
+                raise ValueError(f'filters: an int, a name or an integer tensor [B = {B}], got {f.dtype} '
+                                 f'{tuple(f.shape)}')
+            return f.reshape(-1).to(device)
+        if not isinstance(filters, (int, np.integer)) or isinstance(filters, bool):  # a name
+            if self._filter_names is None or filters not in self._filter_names:
+                raise ValueError(f'unknown filter {filters!r}: the index has '
+                                 f'{list(self._filter_names) if self._filter_names else self.num_filters}')
+            filters = self._filter_names[filters]
+        if not 0 <= int(filters) < self.num_filters:
+            raise ValueError(f'filter {int(filters)} out of range: the index has {self.num_filters}')
+        return torch.full((B,), int(filters), device=device, dtype=torch.int32)
+
+    def search(self, user_emb, k, user_ids=None, oversample=1, filters=None):
+        """-> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first.
+        filters: one of set_filters' filters for every user (its int id or its name), or an integer
+        tensor [B] of ids, negative = that user unfiltered. Columns outside the filter come last,
+        at -inf, and only when fewer than k are allowed."""
         rows = self._rows()
         k = int(k)
         if k < 1 or k > len(self):
             raise ValueError(f'selected index k out of range (k={k}, items={len(self)})')
         if oversample > 1 and self._fp32 is None:
             raise ValueError('oversample > 1 rescores with the fp32 rows: build the index with keep_fp32=True')
+        fid = self._filter_ids(filters, int(user_emb.shape[0]), rows.device)
         _hip.require_device(user_emb)
         _hip.require_device(rows)
         hist = self._history if user_ids is not None else None
         U = user_emb.detach().float().contiguous()
+        flt = dict(filter_ids=fid, filters=self._filters) if fid is not None else {}
         if not fused_supported(self.dim):
             cols, val = self._search_staged(U, k, user_ids, hist)
         elif oversample > 1 and self._dtype != 'fp32':
             C = min(256, int(oversample) * k, len(self))
-            cand, cval = ops.fused_topk(U, rows, C, user_ids, hist, item_exp=self.scale_exp)
+            cand, cval = ops.fused_topk(U, rows, C, user_ids, hist, item_exp=self.scale_exp, **flt)
             exact = ops.rescore_rows(U, self._fp32, cand, cval)
             cols = torch.empty(U.shape[0], k, device=U.device, dtype=torch.int32)
             val = torch.empty(U.shape[0], k, device=U.device, dtype=torch.float32)
             _hip.call('rs_topk_rows', exact.data_ptr(), C, int(U.shape[0]), C, k, cand.data_ptr(), C, 0,
                       cols.data_ptr(), val.data_ptr(), k, ops.stream())
         else:
-            cols, val = ops.fused_topk(U, rows, k, user_ids, hist, item_exp=self.scale_exp)
+            cols, val = ops.fused_topk(U, rows, k, user_ids, hist, item_exp=self.scale_exp, **flt)
         return self.item_ids[cols.long()], val, cols
 
     def columns_of(self, item_ids):
@@ -187,7 +282,7 @@ class ItemIndex:
         cols = torch.where(sorted_ids[pos] == flat, order[pos], torch.full_like(order[pos], -1))
         return cols.reshape(q.shape)
 
-    def rank(self, user_emb, target_item_ids, user_ids=None):
+    def rank(self, user_emb, target_item_ids, user_ids=None, filters=None):
         """-> int32 [B]: the 0-based position of each user's target item in the full ordering that
         search() takes its first k from (value descending, ties by the lower column, the user's
         history at -inf, the target's own membership included), so rank < k exactly when search(k)
@@ -196,8 +291,10 @@ class ItemIndex:
         a column holding a copy of the target's row ties with it bit for bit. Embedding widths the
         kernel does not take (fused_supported) go through the staged pieces chunk by chunk against
         the gathered target score: the same definition, but the target's score is summed in another
-        order than the chunk's, so equal rows need not tie exactly."""
+        order than the chunk's, so equal rows need not tie exactly. filters as search's: a target
+        outside the user's filter ranks behind every allowed column."""
         rows = self._rows()
+        fid = self._filter_ids(filters, int(user_emb.shape[0]), rows.device)
         _hip.require_device(user_emb)
         _hip.require_device(rows)
         hist = self._history if user_ids is not None else None
@@ -206,7 +303,8 @@ class ItemIndex:
         if cols.numel() != U.shape[0]:
             raise ValueError(f'{cols.numel()} target items for {U.shape[0]} users')
         if fused_supported(self.dim):
-            return ops.target_rank(U, rows, cols, user_ids, hist, item_exp=self.scale_exp)
+            flt = dict(filter_ids=fid, filters=self._filters) if fid is not None else {}
+            return ops.target_rank(U, rows, cols, user_ids, hist, item_exp=self.scale_exp, **flt)
         return self._rank_staged(U, cols, user_ids, hist)
 
     def _rank_staged(self, U, cols, user_ids, hist, chunk=65536):
