@@ -731,6 +731,29 @@ int rs_target_rank_filtered(const float* U, int64_t ldu, int B, const void* item
                             const int32_t* hist_idx, int64_t num_users, const int32_t* filter_ids,
                             int64_t fid_stride, const uint32_t* filter_bits, int64_t filter_ld, int num_filters,
                             int splits, void* ws, int64_t ws_bytes, int32_t* out_rank, void* stream);
+/* Hard negatives mined from the index (sample.hip): n catalog columns per user, drawn uniformly
+ * without replacement from a window of ranks of the sweep's own ordering. cand_idx / cand_val
+ * [B, ld_cand >= C] are the first C entries of rs_fused_topk (or its e4m3 / filtered form) for
+ * every user, 1 <= C <= 256; item_ids [N] the catalog's id of each column. A candidate is eligible
+ * when its value is above -inf (not history, not filtered out), its column is in [0, N) and
+ * item_ids[column] != pos_ids[b * pos_stride] (NULL pos_ids: no such test; the test is on the id,
+ * so every column holding the positive's id is out). With E eligible candidates, numbered in
+ * candidate order, the pool is the eligible positions [lo, hi): hi = min(skip + window, E),
+ * lo = min(skip, max(hi - n, 0)), P = hi - lo (the window slides towards the top only as far as
+ * needed to hold n, never past what was fetched). Each pool member gets the key (h << 32) | column,
+ * h = fmix32(column ^ k0) ^ k1 with (k0, k1) the low and high half of
+ * mix64(seed ^ mix64(draw * 0x9e3779b97f4a7c15 + b * 0xd1b54a32d192ed03)); the output is the n
+ * members with the smallest keys in ascending key order: out_ids (item ids) and out_cols
+ * [B, ld_out >= n], out_count[b] = n. 0 < P < n: all P in key order, repeated cyclically up to n,
+ * out_count[b] = P; P = 0: ids and columns -1, out_count[b] = 0. A pure function of its arguments
+ * (no state, no workspace). Checks, before any device call: no null pointer but pos_ids,
+ * 1 <= C <= 256, skip >= 0, 1 <= n <= window, skip + window <= 255, ld_cand >= C, ld_out >= n,
+ * 1 <= N < 2^31. To cover the window the caller fetches C = min(skip + window + 1, N): the + 1 is
+ * the positive's own column. */
+int rs_sample_negatives(const int32_t* cand_idx, const float* cand_val, int64_t ld_cand, int B, int C,
+                        const int64_t* item_ids, int64_t N, const int64_t* pos_ids, int64_t pos_stride,
+                        int skip, int window, int n, uint64_t seed, uint64_t draw, int64_t* out_ids,
+                        int32_t* out_cols, int64_t ld_out, int32_t* out_count, void* stream);
 
 /* ---------------------------------------------------------------- clip + Adam
  * Flat multi-tensor path over a contiguous fp32 range (all parameters packed in one buffer).

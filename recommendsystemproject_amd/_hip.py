@@ -22,6 +22,7 @@ RS_POOL = {'mean': 0, 'sum': 1, 'max': 2}
 MAX_SEGMENTS = 20
 
 vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
+u64 = C.c_uint64
 
 
 class FeatureSeg(C.Structure):
@@ -186,7 +187,9 @@ SIGNATURES = {
                                      vp, i64, i32, i32, vp, i64, vp, vp, i64, vp]),
     'rs_target_rank_filtered': (i32, [vp, i64, i32, vp, i32, i32, i64, i64, i32, vp, i64, vp, i64, vp, vp, i64, vp,
                                       i64, vp, i64, i32, i32, vp, i64, vp, vp]),
-    'rs_collate_ragged': (i32, [vp, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
+    'rs_sample_negatives': (i32, [vp, vp, i64, i32, i32, vp, i64, vp, i64, i32, i32, i32, u64, u64, vp, vp, i64,
+                                  vp, vp]),
+    'rs_collate_ragged':(i32, [vp, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
     'rs_catalog_gather': (i32, [vp, i32, i32, i64, i32, i64, vp, i32, i32, i64, vp, i64, vp, vp]),
     'rs_sqnorm_ws_bytes': (i64, [i64]),
     'rs_grad_sqnorm': (i32, [vp, i64, f32, vp, vp]),

@@ -833,6 +833,49 @@ def fused_topk(U, items, K, user_ids=None, history=None, splits=0, item_exp=None
     return idx, val
 
 
+def sample_negatives(cand, cand_val, item_ids, pos_ids, skip, window, n, seed=0, draw=0):
+    """n catalog columns per user drawn uniformly without replacement from a window of ranks of
+    fused_topk's order (rs_sample_negatives; include/rsys_hip.h has the definition). cand int32 and
+    cand_val fp32 [B, C <= 256]: fused_topk's result; item_ids int64 [N]; pos_ids integer [B] or
+    None: the item id a user never gets. The pool is the eligible candidates (value above -inf, id
+    not the positive's) at eligible positions [skip, skip + window), slid towards the top only as
+    far as needed to hold n. -> (ids int64 [B, n], cols int32 [B, n], count int32 [B]): count < n
+    where the pool had fewer than n members (its members repeat cyclically; ids and cols -1 at
+    count 0). A pure function of (seed, draw) and the candidates. No CPU fallback."""
+    for t in (cand, cand_val, item_ids) + ((pos_ids,) if pos_ids is not None else ()):
+        _hip.require_device(t)
+    if cand.dim() != 2 or cand.dtype != torch.int32 or cand_val.dtype != torch.float32 or cand_val.shape != cand.shape:
+        raise ValueError(f'sample_negatives: cand int32 and cand_val float32 of one shape [B, C], got {cand.dtype} '
+                         f'{tuple(cand.shape)} and {cand_val.dtype} {tuple(cand_val.shape)}')
+    if cand.stride(1) != 1:
+        cand = cand.contiguous()
+    if cand_val.stride(1) != 1 or cand_val.stride(0) != cand.stride(0):
+        cand_val = cand_val.contiguous()
+        cand = cand.contiguous()
+    B, C = int(cand.shape[0]), int(cand.shape[1])
+    ids = item_ids.reshape(-1)
+    if ids.dtype != torch.int64 or ids.stride(0) != 1:
+        ids = ids.long().contiguous()
+    pos, ps = None, 0
+    if pos_ids is not None:
+        pos = pos_ids.reshape(-1)
+        if pos.numel() != B:
+            raise ValueError(f'sample_negatives: {pos.numel()} positive ids for {B} users')
+        if pos.dtype != torch.int64:
+            pos = pos.long()
+        ps = int(pos.stride(0))
+    n = int(n)
+    out_ids = torch.empty(B, max(n, 0), device=cand.device, dtype=torch.int64)
+    out_cols = torch.empty(B, max(n, 0), device=cand.device, dtype=torch.int32)
+    count = torch.empty(B, device=cand.device, dtype=torch.int32)
+    if B == 0:
+        return out_ids, out_cols, count
+    call('rs_sample_negatives', P(cand), P(cand_val), int(cand.stride(0)) if B > 1 else C, B, C, P(ids),
+         int(ids.numel()), P(pos), ps, int(skip), int(window), n, int(seed) & (2 ** 64 - 1), int(draw) & (2 ** 64 - 1),
+         P(out_ids), P(out_cols), n, P(count), stream())
+    return out_ids, out_cols, count
+
+
 def target_rank(U, items, target_cols, user_ids=None, history=None, splits=0, item_exp=None, filter_ids=None,
                 filters=None):
     """For every user the 0-based position of catalog column target_cols[b] in fused_topk's order

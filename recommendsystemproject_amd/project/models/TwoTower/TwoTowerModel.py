@@ -194,6 +194,14 @@ class TwoTowerModel(nn.Module):
         user_emb = self._serving_user_emb(user_inputs)
         return index.rank(user_emb, target_item_ids, user_ids=user_ids, filters=filters)
 
+    def mine_hard_negatives(self, user_inputs, index, n, positive_item_ids=None, **kw):
+        """n hard negatives per user out of `index` by the current model's own ordering
+        (retrieval.ItemIndex.mine_negatives): the user tower alone in eval mode under no_grad, then
+        the sweep and the on-device sampler. -> (ids int64 [B, n], cols int32 [B, n], count int32
+        [B]); kw: skip, window, user_ids, filters, seed, draw."""
+        user_emb = self._serving_user_emb(user_inputs)
+        return index.mine_negatives(user_emb, n, positive_item_ids=positive_item_ids, **kw)
+
     _NAN_MSG = {1: 'Found NaN in User Embedding', 2: 'Found NaN in Item Embedding',
                 4: 'Found NaN in Hard Negative Embedding'}
 

@@ -69,8 +69,12 @@ def backward_seed(loss):
 
 
 def train_step(model, batch_data, optimizer, max_grad_norm=1.0, temperature=0.1,
-               item_id_feature='movie_id_enc', item_id_type='sparse'):
-    """One training step on a device-resident batch; returns the loss as a device scalar."""
+               item_id_feature='movie_id_enc', item_id_type='sparse', miner=None):
+    """One training step on a device-resident batch; returns the loss as a device scalar.
+    miner (hard_negatives.NegativeMiner): mines this batch's hard negatives from the current model
+    and sets batch_data['hard_negatives'] before the forward."""
+    if miner is not None:
+        miner.attach(batch_data)
     optimizer.zero_grad()
     user_emb, pos_item_emb, hard_neg_emb = model(batch_data)
     ids = extract_item_id(batch_data['item_tower'], feature_name=item_id_feature, feature_type=item_id_type)
@@ -100,15 +104,16 @@ def _check_errors(model, optimizer=None):
 
 def train_one_epoch(model, loader, optimizer, device, scheduler=None, log_every_n_batches=100,
                     epoch=None, max_grad_norm=1.0, temperature=0.1, item_id_feature='movie_id_enc',
-                    item_id_type='sparse'):
-    """Same signature and return value (average loss) as training_utils.py:19-70."""
+                    item_id_type='sparse', miner=None):
+    """Same signature and return value (average loss) as training_utils.py:19-70; miner as
+    train_step's."""
     model.train()
     losses = []
     pbar = tqdm(loader, desc=f'Training Epoch {epoch}')
     for batch_idx, batch_data in enumerate(pbar):
         batch_data = to_device(batch_data, device)
         loss = train_step(model, batch_data, optimizer, max_grad_norm, temperature, item_id_feature,
-                          item_id_type)
+                          item_id_type, miner=miner)
         if scheduler is not None:
             scheduler.step()
         losses.append(loss)

@@ -26,6 +26,12 @@ exactly when search(k) with the same filter returns the item.
     index.set_filters({'in_stock': stock_mask, 'kids': index.mask_of(kids_item_ids)})
     item_ids, scores, cols = model.recommend(batch['user_tower'], index, k=20, filters='in_stock')
     item_ids, scores, cols = index.search(user_emb, 20, filters=per_user_filter_ids)   # < 0: none
+
+`mine_negatives` turns the same sweep into training data: n hard negatives per user, drawn on the
+device from a window of ranks of that ordering (csrc/sample.hip), never the positive, the user's
+history or a column outside the user's filter; hard_negatives.NegativeMiner feeds them to a step.
+
+    ids, cols, count = index.mine_negatives(user_emb, 10, positive_item_ids=pos, skip=0, window=31, user_ids=uids)
 """
 from __future__ import annotations
 
@@ -265,6 +271,62 @@ class ItemIndex:
         else:
             cols, val = ops.fused_topk(U, rows, k, user_ids, hist, item_exp=self.scale_exp, **flt)
         return self.item_ids[cols.long()], val, cols
+
+    def mine_negatives(self, user_emb, n, positive_item_ids=None, skip=0, window=None, user_ids=None, filters=None,
+                       seed=0, draw=0):
+        """Hard negatives from the model's own ordering, chosen on the device: for each user, n
+        items drawn uniformly without replacement from the ranks [skip, skip + window) of search's
+        order, counted over the ELIGIBLE items only: not in the user's history (user_ids, as
+        search), inside the user's filter (filters, as search), and not the user's positive
+        (positive_item_ids [B]: the test is on the item id, so every column holding that id is
+        excluded). -> (ids int64 [B, n], cols int32 [B, n], count int32 [B]), ready for
+        ItemCatalog.materialize(ids).
+
+        window=None means min(255 - skip, N). skip leaves out the very top, where unlabelled
+        positives sit. When fewer than skip + window eligible items exist, the window slides
+        towards the top only as far as needed to hold n. count[b] = n normally; a pool of
+        0 < P < n members is returned whole, in drawn order, repeated cyclically, with
+        count[b] = P; an empty pool gives ids and cols -1 and count[b] = 0 (materialize flags
+        such ids), so read count where the filters can be that tight. The draw is a pure function
+        of (seed, draw, user row, column): the same arguments give the same tensors, on every
+        index dtype with the same ordering; advance `draw` per call for fresh samples.
+
+        The sweep fetches C = min(skip + window + 1, N) candidates, the + 1 covering the
+        positive's own column. A catalog that holds the positive's id in several columns can leave
+        the pool that many entries short at its tail; count reports it and nothing compensates.
+        C <= 32 runs the sweep's four-wave small-K kernel, C up to 256 the one-wave one: a shallow
+        window (skip + window <= 31) is the cheap setting for mining every step. Embedding widths
+        outside fused_supported have no staged path here."""
+        rows = self._rows()
+        N = len(self)
+        n, skip = int(n), int(skip)
+        if not fused_supported(self.dim):
+            raise ValueError(f'mine_negatives runs on the fused sweep only: embedding widths that are a multiple '
+                             f'of 16 in [16, 256], got {self.dim}')
+        if skip < 0:
+            raise ValueError(f'mine_negatives: skip = {skip} < 0')
+        window = min(255 - skip, N) if window is None else int(window)
+        if skip + window > 255:
+            raise ValueError(f'mine_negatives: skip + window = {skip + window} > 255, the deepest window the sweep '
+                             f'fetches')
+        if n < 1 or n > window:
+            raise ValueError(f'mine_negatives: n = {n} outside [1, window = {window}]')
+        B = int(user_emb.shape[0])
+        pos = None
+        if positive_item_ids is not None:
+            pos = torch.as_tensor(positive_item_ids).reshape(-1)
+            if pos.numel() != B:
+                raise ValueError(f'mine_negatives: {pos.numel()} positive items for {B} users')
+            pos = pos.to(rows.device)
+        fid = self._filter_ids(filters, B, rows.device)
+        _hip.require_device(user_emb)
+        _hip.require_device(rows)
+        hist = self._history if user_ids is not None else None
+        U = user_emb.detach().float().contiguous()
+        flt = dict(filter_ids=fid, filters=self._filters) if fid is not None else {}
+        C = min(skip + window + 1, N)
+        cand, cval = ops.fused_topk(U, rows, C, user_ids, hist, item_exp=self.scale_exp, **flt)
+        return ops.sample_negatives(cand, cval, self.item_ids, pos, skip, window, n, seed=seed, draw=draw)
 
     def columns_of(self, item_ids):
         """item ids -> their catalog columns, int32 of the same shape on the index's device; -1 for
