@@ -34,16 +34,19 @@ def key(seed, draw, b, col):
     return ((fmix32((col & M32) ^ k0) ^ k1) << 32) | (col & M32)
 
 
+def fmix32_array(h):
+    """fmix32 of a uint64 array holding 32-bit values, vectorised -> uint64 array."""
+    h = h ^ (h >> np.uint64(16))
+    h = (h * np.uint64(0x85ebca6b)) & np.uint64(M32)
+    h = h ^ (h >> np.uint64(13))
+    h = (h * np.uint64(0xc2b2ae35)) & np.uint64(M32)
+    return h ^ (h >> np.uint64(16))
+
+
 def keys_of(seed, draw, b, cols):
     """key() of an int array of columns (0 <= col < 2^31), vectorised -> uint64 array."""
     k0, k1 = stream_keys(seed, draw, b)
-    h = np.asarray(cols, dtype=np.uint64) ^ np.uint64(k0)
-    h ^= h >> np.uint64(16)
-    h = (h * np.uint64(0x85ebca6b)) & np.uint64(M32)
-    h ^= h >> np.uint64(13)
-    h = (h * np.uint64(0xc2b2ae35)) & np.uint64(M32)
-    h ^= h >> np.uint64(16)
-    h ^= np.uint64(k1)
+    h = fmix32_array(np.asarray(cols, dtype=np.uint64) ^ np.uint64(k0)) ^ np.uint64(k1)
     return (h << np.uint64(32)) | np.asarray(cols, dtype=np.uint64)
 
 

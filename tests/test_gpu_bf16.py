@@ -378,12 +378,21 @@ def test_bf16_step_fused_ffn_vs_unfused(monkeypatch):
     assert F.cosine_similarity(g1, g2, dim=0).item() > 0.9999
 
 
-def _bf16_attention_ref(qkv, key_pad, dout, B, L, d, H):
+def _bf16_attention_ref(qkv, key_pad, dout, B, L, d, H, drop=None, rows=False):
     """The bf16 MFMA attention's arithmetic in float64: Q, K, V, dO rounded to bf16; the
     unnormalised probabilities and dS rounded to bf16 where they enter a product; softmax,
     dropout-free dS and the scale in full precision. D = sum_j P_ij dP_ij for L <= 64 (the
     per-wave kernels form it from their register tiles); for L > 64 the key-parallel kernels take
-    D = dO_i . O_i from the fp32 dO and the forward output, which carries the bf16 rounding of P."""
+    D = dO_i . O_i from the fp32 dO and the forward output, which carries the bf16 rounding of P.
+
+    drop: the dropout multipliers Z [B, H, L, L] (0 or zs = 1/(1-p)) of the attention probabilities,
+    applied where csrc/attention.hip applies them. The softmax sum runs over every unmasked key,
+    dropped or not. Forward: the kept unnormalised probabilities are rounded to bf16 and zs scales
+    the output row (attn_fwd_bf16_kernel, attn_fwd_long_kernel). Backward, L <= 64
+    (attn_bwd_bf16_kernel): D = zs sum_j P_ij [kept] dP_ij, dS = P (zs [kept] dP - D), dV = zs
+    bf16(P [kept])^T dO; L > 64 (attn_bwd_long_kernel): D = dO_i . O_i, dS = P (Z dP - D), dV =
+    bf16(P Z)^T dO. rows: csrc/attn_rows.hip, which rounds e Z (forward) and P Z (dV) and forms
+    D = sum_j P_ij Z_ij dP_ij at every L."""
     hd = d // H
     q, k, v = (r16(t).double() for t in qkv.view(B, L, 3, H, hd).permute(2, 0, 3, 1, 4))
     g = r16(dout).double().view(B, L, H, hd).transpose(1, 2)
@@ -394,17 +403,24 @@ def _bf16_attention_ref(qkv, key_pad, dout, B, L, d, H):
     m = (s * sc).amax(-1, keepdim=True)
     e = torch.exp(s * sc - m).masked_fill(mask, 0.0)
     l = e.sum(-1, keepdim=True)
-    out = (r16(e.float()).double() @ v) / l
+    if drop is None:
+        kept, zs = torch.ones_like(e), 1.0
+    else:
+        kept, zs = (drop > 0).double(), drop.max().item()
+    # zs inside the rounding (rows, and the long backward's dV) or outside it (a factor of the row)
+    z_in, z_out = (kept * zs, 1.0) if rows else (kept, zs)
+    out = (r16((e * z_in).float()).double() @ v) / l * z_out
     P = e / l
     dp = g @ v.transpose(-1, -2)
     o32 = out.transpose(1, 2).reshape(B * L, d).float()
     # D_i = sum_j P_ij dP_ij (== dO_i . O_i in exact arithmetic): the kernel forms it from its
     # register tiles, with dP from the bf16-rounded dO and V
-    D = (P * dp).sum(-1, keepdim=True)
-    if L > 64:
+    D = (P * kept * dp).sum(-1, keepdim=True) * zs
+    if L > 64 and not rows:
         D = (dout.double().view(B, L, H, hd).transpose(1, 2) * out).sum(-1, keepdim=True)
-    ds = P * (dp - D)
-    dsb, Pb = r16(ds.float()).double(), r16(P.float()).double()
+        z_in, z_out = kept * zs, 1.0
+    ds = P * (kept * zs * dp - D)
+    dsb, Pb = r16(ds.float()).double(), r16((P * z_in).float()).double() * z_out
     dq = dsb @ k * sc
     dk = dsb.transpose(-1, -2) @ q * sc
     dv = Pb.transpose(-1, -2) @ g

@@ -119,16 +119,18 @@ def _ln(h, g, b):
     return (h - mu) * rs * g + b, mu[:, 0], rs[:, 0]
 
 
-def _check_tail_against_torch(att, res_rows, w, got):
-    """Stage by stage on the kernel's own intermediate rows, so that a bf16 rounding flip of an
-    operand (x1, f1, x2 differ from torch's in the last fp32 bits) cannot enter the comparison:
-    torch fp32 products of bf16-rounded operands differ from the MFMA's in summation order only."""
-    h1, x1, m1, r1, h2, x2, m2, r2, mask, qkv = got
-    h1r = res_rows + r16(att) @ r16(w['Wo']).t() + w['bo']
-    assert torch.allclose(h1, h1r, atol=2e-5, rtol=1e-5)
-    x1r, m1r, r1r = _ln(h1, w['g1'], w['be1'])
-    assert torch.allclose(x1, x1r, atol=1e-4, rtol=1e-4)
-    assert torch.allclose(m1, m1r, atol=1e-5) and torch.allclose(r1, r1r, rtol=1e-4)
+def _allclose(name, a, b, atol, rtol):
+    return torch.allclose(a, b, atol=atol, rtol=rtol)
+
+
+def _check_ffn_against_torch(x1, w, ffn_out, p=0.0, masks=None, close=_allclose):
+    """The feed-forward half of _check_tail_against_torch: ffn_out = (h2, x2, mean2, rstd2, mask) of
+    rs_ffn_fwd_bf16 or of the tail kernel on the rows x1. masks: the multipliers (0 or 1/(1-p)) of
+    the FFN's inner dropout [M, 256] and of dropout2 [M, 64], from somewhere else than the library;
+    the absolute bounds grow by the 1/(1-p) the kept values are scaled by."""
+    h2, x2, m2, r2, mask = ffn_out
+    s = 1.0 / (1.0 - p)
+    za, zb = masks if masks is not None else (1.0, 1.0)
     # f1 never leaves the forward kernel. torch's own f1 would be rounded to bf16 from a sum with
     # another fp32 summation order, and one element that lands on the other side of a rounding
     # boundary moves h2 by far more than the bound below. So f1 is the library's: rs_ffn_bwd_bf16
@@ -136,14 +138,31 @@ def _check_tail_against_torch(att, res_rows, w, got):
     # test_fused_ffn_matches_unfused) and writes it out; torch checks it to one bf16 step and then
     # does the W2 product, the residual and LN2.
     zero = torch.zeros_like(x1)
-    f1 = ops.ffn_bwd_bf16(x1, w['W1'], w['b1'], w['W2'], mask, zero, zero, 0.0)[1].float()
-    f1r = torch.relu(r16(x1) @ r16(w['W1']).t() + w['b1'])
-    assert torch.allclose(f1, f1r, atol=1e-5, rtol=2.0 ** -7)
-    h2r = x1 + f1 @ r16(w['W2']).t() + w['b2']
-    assert torch.allclose(h2, h2r, atol=2e-5, rtol=1e-5)
+    f1 = ops.ffn_bwd_bf16(x1, w['W1'], w['b1'], w['W2'], mask, zero, zero, p)[1].float()
+    f1r = torch.relu(r16(x1) @ r16(w['W1']).t() + w['b1']) * za
+    assert close('f1', f1, f1r, 1e-5 * s, 2.0 ** -7)
+    h2r = x1 + (f1 @ r16(w['W2']).t() + w['b2']) * zb
+    assert close('h2', h2, h2r, 2e-5 * s, 1e-5)
     x2r, m2r, r2r = _ln(h2, w['g2'], w['be2'])
-    assert torch.allclose(x2, x2r, atol=1e-4, rtol=1e-4)
+    assert close('x2', x2, x2r, 1e-4, 1e-4)
     assert torch.allclose(m2, m2r, atol=1e-5) and torch.allclose(r2, r2r, rtol=1e-4)
+
+
+def _check_tail_against_torch(att, res_rows, w, got, p=0.0, masks=None, close=_allclose):
+    """Stage by stage on the kernel's own intermediate rows, so that a bf16 rounding flip of an
+    operand (x1, f1, x2 differ from torch's in the last fp32 bits) cannot enter the comparison:
+    torch fp32 products of bf16-rounded operands differ from the MFMA's in summation order only.
+    masks: the multipliers of dropout1 [M, 64] and of the FFN's two sites (_check_ffn_against_torch).
+    close(name, a, b, atol, rtol): the comparison of each masked stage (default torch.allclose)."""
+    h1, x1, m1, r1, h2, x2, m2, r2, mask, qkv = got
+    s = 1.0 / (1.0 - p)
+    z1 = masks[0] if masks is not None else 1.0
+    h1r = res_rows + (r16(att) @ r16(w['Wo']).t() + w['bo']) * z1
+    assert close('h1', h1, h1r, 2e-5 * s, 1e-5)
+    x1r, m1r, r1r = _ln(h1, w['g1'], w['be1'])
+    assert torch.allclose(x1, x1r, atol=1e-4, rtol=1e-4)
+    assert torch.allclose(m1, m1r, atol=1e-5) and torch.allclose(r1, r1r, rtol=1e-4)
+    _check_ffn_against_torch(x1, w, (h2, x2, m2, r2, mask), p, masks[1:] if masks is not None else None, close)
     if qkv is not None:
         # bf16 storage: within one bf16 ulp (2^-7 relative) of the fp32 product
         qr = r16(x2) @ r16(w['Win']).t() + w['bin']

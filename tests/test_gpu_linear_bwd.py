@@ -50,12 +50,16 @@ CASES = [
 ]
 
 
-def _inputs(B, L, d, dcat, p):
+def _inputs(B, L, d, dcat, p, masks=None):
+    """masks: (mask_a, mask_b) [M, d] of key [4321, 7], sites 0 and 1, from somewhere else than the
+    library (tests/dropout_ref.py); default: rs_dropout_bwd on ones."""
     M = B * L
     t = dict(dx=rnd(M, d, seed=1), cat=rnd(M, dcat, seed=2), W=rnd(d, dcat, seed=3) * 0.2,
              dW0=rnd(d, dcat, seed=4), db0=rnd(d, seed=5), pos0=rnd(L + 3, d, seed=6),
              key=torch.tensor([4321, 7], dtype=torch.int64, device=DEV))
-    if p > 0:
+    if masks is not None:
+        t['mask_a'], t['mask_b'] = masks
+    elif p > 0:
         ones = torch.ones(M, d, device=DEV)
         t['mask_a'] = ops.dropout_bwd(ones.clone(), p, t['key'], 0)
         t['mask_b'] = ops.dropout_bwd(ones.clone(), p, t['key'], 1)

@@ -102,6 +102,14 @@ def _head(segs, M, w, p, err=None):
                             w['key'] if p > 0 else None, 0, 1)
 
 
+def _x0_ref(cat, w, B, masks=None):
+    """x0 = drop_b(drop_a(cat W^T + b) + pos[m % L]) in float64 on the bf16-rounded operands. masks:
+    the two sites' multipliers [M, 64] (0 or 1/(1-p)); None: no dropout."""
+    r16 = lambda t: t.to(torch.bfloat16).double()  # noqa: E731
+    za, zb = (m.double() for m in masks) if masks is not None else (1.0, 1.0)
+    return ((r16(cat) @ r16(w['W']).t() + w['b'].double()) * za + w['pos'].double().repeat(B, 1)) * zb
+
+
 _CASE = {}
 
 
@@ -139,8 +147,7 @@ def test_head_bitwise_against_separate_kernels(kind, B, p, bf16_mode):
     if p == 0:
         # and the pair agrees with torch: exact products of the bf16-rounded operands, so only the
         # fp32 summation order of at most 64 terms differs (the bound of test_gpu_linear_bwd's dcat)
-        r16 = lambda t: t.to(torch.bfloat16).double()  # noqa: E731
-        ref = r16(cat) @ r16(w['W']).t() + w['b'].double() + w['pos'].double().repeat(B, 1)
+        ref = _x0_ref(cat, w, B)
         err, scale = (x0.double() - ref).abs().max().item(), ref.abs().max().item()
         print('x0 err', err, 'scale', scale)
         assert err < 2e-5 * scale, (err, scale)
