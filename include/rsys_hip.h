@@ -754,6 +754,48 @@ int rs_sample_negatives(const int32_t* cand_idx, const float* cand_val, int64_t 
                         const int64_t* item_ids, int64_t N, const int64_t* pos_ids, int64_t pos_stride,
                         int skip, int window, int n, uint64_t seed, uint64_t draw, int64_t* out_ids,
                         int32_t* out_cols, int64_t ld_out, int32_t* out_count, void* stream);
+/* Cluster-pruned (IVF) retrieval (csrc/ivf.hip): rs_fused_topk_filtered restricted, per user, to
+ * the lists the user probes. Given an assignment assign[c] in [0, nlist) of every catalog column
+ * to a list and probe [B, ld_probe >= nprobe] int32, the nprobe DISTINCT lists of each user (the
+ * caller takes rs_fused_topk of U against the centroids [nlist, D]: value descending, ties by the
+ * lower list), the result for user b is the first K entries of rs_fused_topk_filtered's order
+ * (masked score descending, ties by the lower CATALOG column; history and filtered-out columns at
+ * -inf) over the columns c with assign[c] in probe[b, :], and of those only the entries above
+ * -inf; the rest of the K is (column -1, score -inf). A masked column is never returned. With
+ * nprobe == nlist and no filler it is the exhaustive result bit for bit (the scores come from the
+ * same MFMA sequence, which gives the same bits whatever else shares a tile).
+ * The item rows are stored sorted by list: rows [N, D] of item_kind 0 fp32 / 1 bf16 / 2 e4m3
+ * (ldi in elements, bytes for e4m3; item_exp as rs_fused_topk_filtered's), row r = catalog column
+ * perm[r]; list l is rows [list_off[l], list_off[l + 1]), list_off int32 [nlist + 1] from 0 to N,
+ * ascending perm inside a list. History, user ids and filters exactly as rs_fused_topk_filtered's,
+ * on catalog columns.
+ * Three calls on one stream, none of which synchronises with the host, sharing one workspace of
+ * rs_ivf_ws_bytes(B, nprobe, nlist, K, layout) bytes (host only, 16-byte aligned; layout nullable,
+ * int64[8]: [0] the bound on the number of work items, ceil(B nprobe / 32) + min(nlist, B nprobe),
+ * which is the scan's grid; byte offsets of [1] the candidate words uint64 [B nprobe][K], [2] the
+ * work items int32 [bound][4] = {list, first pair slot, pairs (1..32), 0}, list -1 in the surplus
+ * ones, [3] the pair indices p = b * nprobe + slot grouped by list, int32 [B nprobe], [4] scatter
+ * cursors, [5] pair offsets and [6] work-item offsets per list, int32 [nlist + 1]; [7] the bytes):
+ *   rs_ivf_group: the (user, slot) pairs grouped by list and cut into work items of at most 32
+ *     users. The order of pairs inside a list may differ between runs; no result depends on it.
+ *     A probe entry outside [0, nlist) contributes nothing.
+ *   rs_ivf_scan: a wave per work item sweeps its list and leaves each pair's K best as sorted
+ *     words (order key of the score << 32 | ~column); the filler word 0 where the list has fewer.
+ *   rs_ivf_merge: per user the best K of its nprobe runs by the 64-bit word -> out_cols int32 and
+ *     out_val fp32 [B, ld_out >= K]; entries at -inf and fillers become (-1, -inf).
+ * Checks, before any device call: D a multiple of 16 in [16, 256], 1 <= K <= 256, 1 <= nlist <=
+ * 65536, 1 <= nprobe <= min(nlist, 256), 1 <= N < 2^31, B nprobe < 2^31, rows of U and the item
+ * rows 16-byte aligned, the workspace present and large enough. */
+int64_t rs_ivf_ws_bytes(int B, int nprobe, int nlist, int K, int64_t* layout);    /* host only */
+int rs_ivf_group(const int32_t* probe, int64_t ld_probe, int B, int nprobe, int nlist, int K, void* ws,
+                 int64_t ws_bytes, void* stream);
+int rs_ivf_scan(const float* U, int64_t ldu, int B, const void* rows, int item_kind, int item_exp, int64_t ldi,
+                int64_t N, int D, int K, const int32_t* perm, const int32_t* list_off, int nlist, int nprobe,
+                const int64_t* user_ids, int64_t uid_stride, const int64_t* hist_off, const int32_t* hist_idx,
+                int64_t num_users, const int32_t* filter_ids, int64_t fid_stride, const uint32_t* filter_bits,
+                int64_t filter_ld, int num_filters, void* ws, int64_t ws_bytes, void* stream);
+int rs_ivf_merge(int B, int nprobe, int nlist, int K, void* ws, int64_t ws_bytes, int32_t* out_cols,
+                 float* out_val, int64_t ld_out, void* stream);
 
 /* ---------------------------------------------------------------- clip + Adam
  * Flat multi-tensor path over a contiguous fp32 range (all parameters packed in one buffer).

@@ -189,6 +189,11 @@ SIGNATURES = {
                                       i64, vp, i64, i32, i32, vp, i64, vp, vp]),
     'rs_sample_negatives': (i32, [vp, vp, i64, i32, i32, vp, i64, vp, i64, i32, i32, i32, u64, u64, vp, vp, i64,
                                   vp, vp]),
+    'rs_ivf_ws_bytes': (i64, [i32, i32, i32, i32, vp]),
+    'rs_ivf_group': (i32, [vp, i64, i32, i32, i32, i32, vp, i64, vp]),
+    'rs_ivf_scan': (i32, [vp, i64, i32, vp, i32, i32, i64, i64, i32, i32, vp, vp, i32, i32, vp, i64, vp, vp, i64, vp,
+                          i64, vp, i64, i32, vp, i64, vp]),
+    'rs_ivf_merge': (i32, [i32, i32, i32, i32, vp, i64, vp, vp, i64, vp]),
     'rs_collate_ragged':(i32, [vp, i32, i32, vp, i64, vp, i32, i32, vp, vp, vp]),
     'rs_catalog_gather': (i32, [vp, i32, i32, i64, i32, i64, vp, i32, i32, i64, vp, i64, vp, vp]),
     'rs_sqnorm_ws_bytes': (i64, [i64]),

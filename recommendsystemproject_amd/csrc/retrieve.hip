@@ -35,22 +35,11 @@
 // must start inside a word (few columns a split: small catalogs only) test the column's bit on
 // admission instead, as history does. The rank kernel funnel-shifts two words there; it takes
 // the sign-trick path only for blocks whose 32 bits are set for every user of the wave.
+#include "retrieve_list.h"
 #include "retrieve_tile.h"
 
 namespace rs {
 namespace {
-
-constexpr int kFtMaxK = 256;
-constexpr int kFtSmallK = 32;
-
-__device__ __forceinline__ uint32_t ft_order_key(float v) {
-  const uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending uint order == ascending float
-}
-__device__ __forceinline__ float ft_key_value(uint32_t k) {
-  const uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
 
 // Catalog filters: a user's packed row as its first word's index in `bits` (one register; -1:
 // unfiltered) and the 32 bits of the block of columns [colbase, colbase + 32), bit i = column
@@ -120,41 +109,6 @@ struct FtArgs {
   FtFilter f;  // the FILT instances only
 };
 
-// the best K of list L (n entries) to L[0 .. K), sorted descending; thr = value of the K-th
-template <int CAP>
-__device__ __forceinline__ void ft_prune_row(unsigned long long* L, int* cnt, float* thr, int K, int lane) {
-  constexpr int J = (CAP + 63) / 64;
-  const int n = min(__builtin_amdgcn_readfirstlane(*cnt), CAP);
-  unsigned long long own[J];
-  int rank[J];
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int i = lane + 64 * j;
-    own[j] = i < n ? L[i] : 0ull;
-    rank[j] = 0;
-  }
-  // unrolled: the broadcast reads of a batch are in flight together (one exposed LDS round trip
-  // per entry otherwise)
-#pragma unroll 8
-  for (int q = 0; q < n; ++q) {
-    const unsigned long long v = L[q];  // broadcast read
-#pragma unroll
-    for (int j = 0; j < J; ++j) rank[j] += v > own[j] ? 1 : 0;
-  }
-  __builtin_amdgcn_wave_barrier();  // every read of the old list before the first write
-#pragma unroll
-  for (int j = 0; j < J; ++j) {
-    const int i = lane + 64 * j;
-    if (i < n && rank[j] < K) {
-      L[rank[j]] = own[j];
-      if (rank[j] == K - 1) *thr = ft_key_value((uint32_t)(own[j] >> 32));
-    }
-  }
-  if (lane == 0) *cnt = min(n, K);
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
 template <int DP, FtElem EK, int KB, bool FILT>
 __global__ __launch_bounds__((FtCfg<DP, EK, KB>::NT)) void fused_topk_kernel(FtArgs a) {
   // the one unfiltered instance that fills all 512 registers takes 32-item tiles when filtered
@@ -189,9 +143,9 @@ __global__ __launch_bounds__((FtCfg<DP, EK, KB>::NT)) void fused_topk_kernel(FtA
   // admit nothing
   if (h == 0) {
     s_cnt[lrow] = 0;
-    s_thr[lrow] = o_ok ? __uint_as_float(0x7fc00000u) : INFINITY;
+    s_thr[lrow] = o_ok ? __uint_as_float(kFtNeverHeldK) : INFINITY;
   }
-  float thr = o_ok ? __uint_as_float(0x7fc00000u) : INFINITY;
+  float thr = o_ok ? __uint_as_float(kFtNeverHeldK) : INFINITY;
 
   int64_t h_lo = 0, h_hi = 0;  // the user's CSR slice (sorted ascending)
   if (o_ok && a.user_ids && a.hist_off && a.hist_idx) {

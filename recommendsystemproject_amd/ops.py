@@ -833,6 +833,72 @@ def fused_topk(U, items, K, user_ids=None, history=None, splits=0, item_exp=None
     return idx, val
 
 
+def ivf_workspace(B, nprobe, nlist, K):
+    """(bytes, layout) of the cluster-pruned search's workspace (rs_ivf_ws_bytes, host only):
+    layout = [work-item bound, then the byte offsets of the candidate words, the work items, the
+    grouped pairs, the cursors, the pair offsets, the work-item offsets, and the bytes]."""
+    import ctypes
+    lay = (ctypes.c_int64 * 8)()
+    nbytes = _hip.lib().rs_ivf_ws_bytes(int(B), int(nprobe), int(nlist), int(K), ctypes.addressof(lay))
+    return int(nbytes), [int(v) for v in lay]
+
+
+def ivf_topk(U, rows_sorted, perm, list_off, centroids, K, nprobe, user_ids=None, history=None, item_exp=None,
+             filter_ids=None, filters=None):
+    """Cluster-pruned top-K (csrc/ivf.hip): fused_topk's result restricted, per user, to the
+    catalog columns of the nprobe lists whose centroids score highest against the user. U [B, D]
+    fp32; rows_sorted [N, D] (fp32, bf16 or float8_e4m3fn with item_exp) the item rows sorted by
+    list, row r = catalog column perm[r] (int32 [N], ascending inside a list), list l = rows
+    [list_off[l], list_off[l + 1]) (int32 [nlist + 1]); centroids fp32 [nlist, D]. The coarse step
+    is fused_topk(U, centroids, nprobe). user_ids / history / filter_ids / filters as fused_topk's,
+    on catalog columns. -> (cols int32 [B, K], val fp32 [B, K]): masked score descending, ties by
+    the lower catalog column, only entries above -inf; the rest (-1, -inf). The coarse
+    step and the three stages (rs_ivf_group / rs_ivf_scan / rs_ivf_merge) run on the current stream
+    with no host synchronisation. No CPU fallback."""
+    use_hist = history is not None and user_ids is not None
+    for t in (U, rows_sorted, perm, list_off, centroids) + ((user_ids,) + tuple(history[:2]) if use_hist else ()):
+        _hip.require_device(t)
+    suffix, kind = _item_kind('ivf_topk', rows_sorted, item_exp)
+    U = U.float()
+    if U.stride(1) != 1 or U.stride(0) % 4 or U.data_ptr() % 16:
+        U = U.contiguous()
+    items = rows_sorted
+    if items.stride(1) != 1 or (items.stride(0) * items.element_size()) % 16 or items.data_ptr() % 16:
+        items = items.contiguous()
+    B, D = int(U.shape[0]), int(U.shape[1])
+    N, nlist = int(items.shape[0]), int(centroids.shape[0])
+    K, nprobe = int(K), int(nprobe)
+    if perm.dtype != torch.int32 or list_off.dtype != torch.int32 or perm.numel() != N or list_off.numel() != nlist + 1:
+        raise ValueError(f'ivf_topk: perm int32 [N = {N}] and list_off int32 [nlist + 1 = {nlist + 1}], got '
+                         f'{perm.dtype} {tuple(perm.shape)} and {list_off.dtype} {tuple(list_off.shape)}')
+    if centroids.dim() != 2 or int(centroids.shape[1]) != D or centroids.dtype != torch.float32:
+        raise ValueError(f'ivf_topk: centroids fp32 [nlist, D = {D}], got {centroids.dtype} {tuple(centroids.shape)}')
+    if not 1 <= nprobe <= min(nlist, 256):
+        raise ValueError(f'ivf_topk: nprobe = {nprobe}, must be in [1, min(nlist = {nlist}, 256)]')
+    cols = torch.empty(B, K, device=U.device, dtype=torch.int32)
+    val = torch.empty(B, K, device=U.device, dtype=torch.float32)
+    if B == 0:
+        return cols, val
+    probe, _ = fused_topk(U, centroids, nprobe)
+    nbytes, _ = ivf_workspace(B, nprobe, nlist, K)
+    w = ws(nbytes, U.device)
+    uid, us, off, hidx, nu = None, 0, None, None, 0
+    if use_hist:
+        uid = user_ids if user_ids.dtype == torch.int64 else user_ids.long()
+        us = int(uid.stride(0))
+        off, hidx, nu = history
+    fid, fs, bits, fld, F = None, 0, None, 0, 0
+    if filter_ids is not None:
+        fid, fs, bits, fld, F = _filter_args('ivf_topk', filter_ids, filters, B, N)
+    st = stream()
+    call('rs_ivf_group', P(probe), nprobe, B, nprobe, nlist, K, P(w), nbytes, st)
+    call('rs_ivf_scan', P(U), int(U.stride(0)), B, P(items), 2 if suffix else kind, kind if suffix else 0,
+         int(items.stride(0)), N, D, K, P(perm), P(list_off), nlist, nprobe, P(uid), us, P(off), P(hidx), int(nu),
+         P(fid), fs, P(bits), fld, F, P(w), nbytes, st)
+    call('rs_ivf_merge', B, nprobe, nlist, K, P(w), nbytes, P(cols), P(val), K, st)
+    return cols, val
+
+
 def sample_negatives(cand, cand_val, item_ids, pos_ids, skip, window, n, seed=0, draw=0):
     """n catalog columns per user drawn uniformly without replacement from a window of ranks of
     fused_topk's order (rs_sample_negatives; include/rsys_hip.h has the definition). cand int32 and

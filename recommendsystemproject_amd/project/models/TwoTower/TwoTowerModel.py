@@ -179,12 +179,18 @@ class TwoTowerModel(nn.Module):
         finally:
             self.train(was_training)
 
-    def recommend(self, user_inputs, index, k, user_ids=None, oversample=1, filters=None):
+    def recommend(self, user_inputs, index, k, user_ids=None, oversample=1, filters=None, nprobe=None):
         """The k best items of `index` (retrieval.ItemIndex) for each user of `user_inputs` (a
         user-tower batch): the user tower alone in eval mode under no_grad, then index.search.
         -> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first. filters:
-        one of the index's catalog filters (ItemIndex.set_filters) by id or name, or ids [B]."""
+        one of the index's catalog filters (ItemIndex.set_filters) by id or name, or ids [B].
+        nprobe: for a retrieval.IvfIndex, the number of lists each user probes (its search takes
+        no oversample; entries past the probed lists' eligible columns are -1 / -inf)."""
         user_emb = self._serving_user_emb(user_inputs)
+        if nprobe is not None:
+            if oversample != 1:
+                raise ValueError('recommend: nprobe (an IvfIndex search) takes no oversample')
+            return index.search(user_emb, k, nprobe, user_ids=user_ids, filters=filters)
         return index.search(user_emb, k, user_ids=user_ids, oversample=oversample, filters=filters)
 
     def rank_targets(self, user_inputs, index, target_item_ids, user_ids=None, filters=None):

@@ -32,6 +32,13 @@ device from a window of ranks of that ordering (csrc/sample.hip), never the posi
 history or a column outside the user's filter; hard_negatives.NegativeMiner feeds them to a step.
 
     ids, cols, count = index.mine_negatives(user_emb, 10, positive_item_ids=pos, skip=0, window=31, user_ids=uids)
+
+IvfIndex is a cluster-pruned view of an ItemIndex for catalogs where the full sweep is the cost: the
+rows grouped into lists around centroids, a search sweeping only the `nprobe` lists closest to each
+user (csrc/ivf.hip), defined as the exhaustive search restricted to those lists, bit for bit.
+
+    ivf = IvfIndex.build(index, nlist=1024)
+    item_ids, scores, cols = model.recommend(batch['user_tower'], ivf, k=20, user_ids=uids, nprobe=16)
 """
 from __future__ import annotations
 
@@ -424,3 +431,135 @@ class ItemIndex:
         pos = torch.searchsorted(keys, q.contiguous()).clamp(max=total - 1)
         hit = (keys[pos] == q) & ok.view(-1, 1)
         return val.masked_fill(hit, float('-inf'))
+
+
+class IvfIndex:
+    """A cluster-pruned (IVF) view of an ItemIndex: the catalog's rows grouped into `nlist` lists
+    around centroids on the sphere; a search scores the user against the centroids and sweeps only
+    the `nprobe` closest lists (csrc/ivf.hip) instead of the whole catalog.
+
+    The result is DEFINED as the base index's exhaustive search restricted to the probed lists:
+    masked score descending, ties by the lower catalog column, the user's history and the columns
+    outside the user's filter excluded, over the columns c with assign[c] in the user's probed
+    lists. Scores have the bits the exhaustive sweep gives the same (user, column), so with
+    nprobe == nlist the two searches agree exactly. Only entries above -inf are returned: when the
+    probed lists hold fewer than k eligible columns the rest is (item id -1, score -inf, column -1);
+    unlike ItemIndex.search a masked column never comes back.
+
+    The base index stays as `base`: history (set_history), filters (set_filters), item_ids,
+    columns_of, mask_of, rank and mine_negatives are the base's, stay exhaustive, and what is set
+    there applies to search here. Columns are the catalog's throughout; the cluster-sorted order is
+    internal.
+
+    Cost beside the base: one more copy of the rows (in the base's dtype), 4 N bytes of `perm` and
+    nlist * D * 4 bytes of centroids.
+
+        ivf = IvfIndex.build(index, nlist=1024)
+        item_ids, scores, cols = ivf.search(user_emb, 20, nprobe=16, user_ids=uids)
+    """
+
+    def __init__(self, base, centroids, rows_sorted, perm, list_off, assign):
+        self.base = base
+        self.centroids = centroids      # fp32 [nlist, D]
+        self.rows_sorted = rows_sorted  # the base's rows, grouped by list
+        self.perm = perm                # int32 [N]: the catalog column of sorted row r
+        self.list_off = list_off        # int32 [nlist + 1]
+        self.assign = assign            # int32 [N]: the list of catalog column c
+
+    @property
+    def nlist(self):
+        return int(self.centroids.shape[0])
+
+    def __len__(self):
+        return len(self.base)
+
+    @classmethod
+    def from_assignment(cls, index, centroids, assign):
+        """The index for a given clustering: centroids fp32 [nlist, D], assign integer [N] with
+        values in [0, nlist) (a list may be empty). The sort by list is stable, so the rows of one
+        list stay in ascending catalog column. Runs on the base's device, host tensors included."""
+        rows = index._rows()
+        N, D = int(rows.shape[0]), int(rows.shape[1])
+        dev = rows.device
+        centroids = torch.as_tensor(centroids).detach().float().to(dev).contiguous()
+        if centroids.dim() != 2 or int(centroids.shape[1]) != D or centroids.shape[0] < 1:
+            raise ValueError(f'from_assignment: centroids [nlist >= 1, D = {D}], got {tuple(centroids.shape)}')
+        nlist = int(centroids.shape[0])
+        if nlist > 65536:
+            raise ValueError(f'from_assignment: nlist = {nlist}, at most 65536')
+        if not fused_supported(D):
+            raise ValueError(f'an IvfIndex takes embedding widths that are a multiple of 16 in [16, 256], got {D}')
+        a = torch.as_tensor(assign).detach().reshape(-1)
+        if a.is_floating_point() or a.dtype == torch.bool or a.numel() != N:
+            raise ValueError(f'from_assignment: assign integer [N = {N}], got {a.dtype} {tuple(a.shape)}')
+        a = a.to(dev).long()
+        if N and (int(a.min()) < 0 or int(a.max()) >= nlist):
+            raise ValueError(f'from_assignment: assign values outside [0, nlist = {nlist})')
+        order = torch.sort(a, stable=True).indices
+        counts = torch.bincount(a, minlength=nlist)
+        list_off = torch.zeros(nlist + 1, device=dev, dtype=torch.int64)
+        list_off[1:] = torch.cumsum(counts, 0)
+        # float8 rows move as bytes (no gather kernel for the dtype)
+        src = rows.view(torch.uint8) if rows.dtype == torch.float8_e4m3fn else rows
+        rows_sorted = src.index_select(0, order).contiguous()
+        if rows.dtype == torch.float8_e4m3fn:
+            rows_sorted = rows_sorted.view(torch.float8_e4m3fn)
+        return cls(index, centroids, rows_sorted, order.int().contiguous(), list_off.int().contiguous(),
+                   a.int().contiguous())
+
+    @classmethod
+    def build(cls, index, nlist, iters=10, seed=0):
+        """Spherical k-means on the base's fp32 rows: `nlist` distinct rows drawn by a seeded CPU
+        generator as the first centroids, then `iters` rounds of assignment (ops.fused_topk of the
+        rows against the centroids, K = 1: ties to the lower list) and update (the normalised mean
+        of a list's members, summed in column order; an emptied list keeps its centroid). The same
+        seed gives the same index, bit for bit. Off the serving path: it synchronises freely."""
+        X = index.embeddings
+        if X is None:
+            raise ValueError('IvfIndex.build clusters the fp32 rows: build the base index with keep_fp32=True')
+        N, D = int(X.shape[0]), int(X.shape[1])
+        nlist, iters = int(nlist), int(iters)
+        if not 1 <= nlist <= min(N, 65536):
+            raise ValueError(f'IvfIndex.build: nlist = {nlist}, must be in [1, min(N = {N}, 65536)]')
+        if iters < 0:
+            raise ValueError(f'IvfIndex.build: iters = {iters} < 0')
+        if not fused_supported(D):
+            raise ValueError(f'an IvfIndex takes embedding widths that are a multiple of 16 in [16, 256], got {D}')
+        _hip.require_device(X)
+        g = torch.Generator(device='cpu')
+        g.manual_seed(int(seed))
+        first = torch.randperm(N, generator=g)[:nlist].to(X.device)
+        C = torch.nn.functional.normalize(X.index_select(0, first), dim=1).contiguous()
+        for _ in range(iters):
+            a = ops.fused_topk(X, C, 1)[0].view(-1).long()
+            # member sums in column order (a stable sort, then one sequential sum per list and
+            # dimension): index_add_'s atomics would make the centroids' last bits vary by run
+            order = torch.sort(a, stable=True).indices
+            sums = torch.segment_reduce(X.index_select(0, order), 'sum', lengths=torch.bincount(a, minlength=nlist),
+                                        axis=0, unsafe=True)
+            norm = sums.norm(dim=1, keepdim=True)
+            C = torch.where(norm > 0, sums / norm.clamp(min=1e-30), C).contiguous()
+        assign = ops.fused_topk(X, C, 1)[0].view(-1)
+        return cls.from_assignment(index, C, assign)
+
+    def search(self, user_emb, k, nprobe, user_ids=None, filters=None):
+        """-> (item_ids int64 [B, k], scores fp32 [B, k], cols int32 [B, k]), best first, from the
+        nprobe lists closest to each user; (-1, -inf, -1) where the probed lists hold fewer than k
+        eligible columns. user_ids and filters as ItemIndex.search's (the base's history and
+        filters). Nothing here synchronises with the host."""
+        base = self.base
+        k, nprobe = int(k), int(nprobe)
+        if k < 1 or k > 256:
+            raise ValueError(f'IvfIndex.search: k = {k}, must be in [1, 256]')
+        if not 1 <= nprobe <= min(self.nlist, 256):
+            raise ValueError(f'IvfIndex.search: nprobe = {nprobe}, must be in [1, min(nlist = {self.nlist}, 256)]')
+        fid = base._filter_ids(filters, int(user_emb.shape[0]), self.rows_sorted.device)
+        _hip.require_device(user_emb)
+        _hip.require_device(self.rows_sorted)
+        hist = base._history if user_ids is not None else None
+        U = user_emb.detach().float().contiguous()
+        flt = dict(filter_ids=fid, filters=base._filters) if fid is not None else {}
+        cols, val = ops.ivf_topk(U, self.rows_sorted, self.perm, self.list_off, self.centroids, k, nprobe, user_ids,
+                                 hist, item_exp=base.scale_exp, **flt)
+        ids = torch.where(cols >= 0, base.item_ids[cols.clamp(min=0).long()], torch.full_like(cols, -1, dtype=torch.int64))
+        return ids, val, cols
