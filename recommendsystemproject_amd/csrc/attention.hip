@@ -33,6 +33,28 @@ __device__ __forceinline__ bool map_bh(int B, int H, int& b, int& h) {
 
 __host__ inline int bh_grid(int B, int H) { return ((B + 7) / 8) * 8 * H; }
 
+// x * y rounded to fp32 and never fused into a following add. The fp32 forwards scale a score for
+// the row maximum and again for the exponent; the two must be the same number, so that the largest
+// key's exponent is exactly 0 and its probability exactly 1. Contracted into fma(s, scale, -m) the
+// exponent was the product's rounding residue instead, and a row with a single valid key gave
+// (p V) (1 / p) with p = 1 +- an ulp, not V.
+__device__ __forceinline__ float mul_rounded(float x, float y) {
+  float v = x * y;
+  asm("" : "+v"(v));
+  return v;
+}
+
+// scale * (q . k) of the VALU forward, which forms every score twice (for the row maximum, then for
+// the exponent): one explicit fma chain, so that both passes round alike. Left to contraction, the
+// compiler fused a different number of the dot's terms in the two loops at head_dim 16.
+template <int HD>
+__device__ __forceinline__ float scaled_score(const float (&q)[HD], const float* __restrict__ k, float scale) {
+  float s = 0.f;
+#pragma unroll
+  for (int c = 0; c < HD; ++c) s = __builtin_fmaf(q[c], k[c], s);
+  return mul_rounded(s, scale);
+}
+
 template <int HD, bool DROP>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__ qkv,
                                                        const uint8_t* __restrict__ key_pad,
@@ -69,20 +91,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(const float* __restrict__
     float m = -INFINITY;
     for (int j = 0; j < L; ++j) {
       if (msk[j] != 0.f) continue;
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < HD; ++c) s += q[c] * Ks[j * HD + c];
-      m = fmaxf(m, s * scale);
+      m = fmaxf(m, scaled_score<HD>(q, &Ks[j * HD], scale));
     }
     float l = 0.f, o[HD];
 #pragma unroll
     for (int c = 0; c < HD; ++c) o[c] = 0.f;
     for (int j = 0; j < L; ++j) {
       if (msk[j] != 0.f) continue;
-      float s = 0.f;
-#pragma unroll
-      for (int c = 0; c < HD; ++c) s += q[c] * Ks[j * HD + c];
-      const float p = expf(s * scale - m);
+      const float p = expf(scaled_score<HD>(q, &Ks[j * HD], scale) - m);
       l += p;
       // attention-probability dropout acts on softmax(s) (= p / l): scale the V weight only
       const float pz = DROP ? p * keep_mult(dk, ((uint64_t)bh * L + i) * L + j) : p;
@@ -271,8 +287,10 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(
 #pragma unroll
     for (int tk = 0; tk < NT; ++tk)
 #pragma unroll
-      for (int e = 0; e < 4; ++e)
-        if (kok[tk][e]) m = fmaxf(m, sv[tk][e] * scale2);
+      for (int e = 0; e < 4; ++e) {
+        sv[tk][e] = mul_rounded(sv[tk][e], scale2);  // scaled once, for the max and for the exponent
+        if (kok[tk][e]) m = fmaxf(m, sv[tk][e]);
+      }
     m = quad_max(m);
     float l = 0.f;
     const int i = tq * 16 + r;
@@ -283,7 +301,7 @@ __global__ __launch_bounds__(256) void attn_fwd_mfma_kernel(
       if (DROP) keep4_32(dk, rowbase + tk * 16 + 4 * q, mk);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float pv = kok[tk][e] ? exp2f(sv[tk][e] * scale2 - m) : 0.f;
+        const float pv = kok[tk][e] ? exp2f(sv[tk][e] - m) : 0.f;
         l += pv;
         sv[tk][e] = DROP ? pv * mk[e] : pv;
       }
